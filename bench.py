@@ -1,8 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- mW interactions/s on the 4096-molecule ice-Ih workload.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step).
+--full adds everything else, as measured before the option existed: the CPU baseline (--no-cpu-baseline
+drops it), per-kernel timings and roofline blocks, the device copy ceiling, the checks of walker 0
+against the golden vector and of the synchronised tables, and the secondary and production-driver
+measurements (--no-secondary drops those).
+--dump-outputs DIR writes what the last timed step computed on rank 0 as DIR/<name>.npy (float64):
+model_energy (every walker's full-box energy), trial_energy_old / trial_energy_new (old and new local
+energy of every trial move, walker-major; a fixed seeded sample, with its indices in trial_sample_index,
+when they would pass DUMP_MAX_BYTES) and interaction_counts (pairs, triplets, move interactions old,
+new).  The inputs depend on the arguments only, so two builds can be compared output for output.
 
 Workload (BASELINE.json configs[1], "ih4096_t015"): every rank holds `--walkers`
 independent walkers, each a 4096-molecule hexagonal-ice box (8x8x8 of the 8-atom
@@ -37,6 +48,23 @@ if ROOT not in sys.path:
 N_MOL = 4096
 NBINS = 101            # examples/ice1_gen_weights/ice.input
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
+DUMP_MAX_BYTES = 64 * 10**6   # --dump-outputs: all arrays together stay below this
+
+
+def dump_outputs(out_dir, model_energy, e_old, e_new, counts):
+    """The last timed step's results as float64 .npy files (see the module docstring)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"model_energy": model_energy, "interaction_counts": np.asarray(counts, dtype=np.float64)}
+    n = len(e_old)
+    room = (DUMP_MAX_BYTES - 8 * (len(model_energy) + len(counts)) - 4096) // 8     # (4096: the .npy headers)
+    if 2 * n <= room:
+        arrays["trial_energy_old"], arrays["trial_energy_new"] = e_old, e_new
+    else:                                     # a fixed, seeded sample of the moves, the same for the same arguments
+        idx = np.sort(np.random.default_rng(20250228).choice(n, size=room // 3, replace=False))
+        arrays["trial_energy_old"], arrays["trial_energy_new"] = e_old[idx], e_new[idx]
+        arrays["trial_sample_index"] = idx
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def make_walkers(first_walker, count, sigma):
@@ -538,6 +566,85 @@ def self_launch(n, json_fd):
     return 0
 
 
+def full_measurements(args, em, rank, W, M, gold, n_gold, i_full, i_moves, so, sn, list_cold_ms, list_ms, mn, mx):
+    """--full, after the timed steps: per-kernel timings and roofline blocks, the device copy ceiling and walker 0 against the
+    golden vector.  Every rank launches the same kernels; the entries of the result line come back on rank 0 (None elsewhere)."""
+    import torch
+    entries = em.neighbour_total(1, W)
+    bytes_full = W * N_MOL * (24 + 8) + 8 * entries             # SURVEY.md 8(d): N*(24 + 8*nbar + 8)
+    bytes_moves = 24 * (2 * W * M) + 32 * (so + sn)             # 24 + 8*slots + 24*slots per evaluation
+    nk = min(args.steps, 2000)
+    ms_full = float(np.mean([em.timer_ms(2 * k) for k in range(nk)]))
+    ms_moves = float(np.mean([em.timer_ms(2 * k + 1) for k in range(nk)]))
+    e_walker0 = em.model_energy_fetch(1, 1)[0]
+    # The step's full-box launch also leaves every molecule's moments behind for the step's move kernel (its moment path, DESIGN.md
+    # 3.2): ~50 us of stores on top of the evaluation.  The kernel of configs[1] by itself -- compute_model_energy of every walker,
+    # nothing else -- is timed here, outside the step loop, and is what `roofline_model_energy` describes.
+    for k in range(24):                              # one event pair per launch, each launch behind a launch of the move kernels -- the
+        em.moves_launch()                            # conditions the kernel has inside a step (a bracket of back-to-back launches lets their
+        em.timer_start(4010 + k)                     # tails and heads overlap: 7 % less per launch; launches on an idle GPU: 8 % more)
+        em.model_energy_launch(1, W)
+        em.timer_stop(4010 + k)
+    ms_full_plain = float(np.mean([em.timer_ms(4010 + k) for k in range(4, 24)]))
+    moves_err = None
+    if gold is not None and n_gold:    # what the LAST timed k_move_energy launch left on the device, against the reference's values
+        eo, en = em.moves_fetch()
+        moves_err = float(max(np.max(np.abs(eo[:n_gold] - gold["trial_old"][:n_gold]) / np.abs(gold["trial_old"][:n_gold])),
+                              np.max(np.abs(en[:n_gold] - gold["trial_new"][:n_gold]) / np.abs(gold["trial_new"][:n_gold]))))
+        if not moves_err <= 1e-10:
+            raise SystemExit(f"walker 0: old/new local energies of the timed move kernel differ from the golden vector (max rel {moves_err:.3e})")
+    if rank != 0:
+        return None
+
+    # the ceiling a plain device-to-device copy reaches on this box (SURVEY.md 8(d): report against nominal AND this)
+    nbytes = 1 << 30
+    a = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    b = torch.empty_like(a)
+    b.copy_(a); torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(10):
+        b.copy_(a)
+    t1.record(); torch.cuda.synchronize()
+    copy_gbs = 2.0 * nbytes * 10 / (t0.elapsed_time(t1) * 1e-3) / 1e9          # bytes read + bytes written
+    del a, b
+
+    sanity = None
+    if gold is not None:
+        ref = float(gold["model_energy"])
+        sanity = abs(e_walker0 - ref) / abs(ref)
+        if sanity > 1e-10:
+            raise SystemExit(f"walker 0 energy {e_walker0!r} differs from the golden vector {ref!r}")
+    dominant = "k_model_energy" if ms_full >= ms_moves else "k_move_energy"
+    counters = load_counters(W, M)
+    rl = {"k_model_energy": kernel_roofline("k_model_energy", bytes_full, ms_full_plain, W * N_MOL, counters, copy_gbs),
+          "k_move_energy": kernel_roofline("k_move_energy", bytes_moves, ms_moves, W * M, counters, copy_gbs)}
+    entries_bytes = W * N_MOL * (24 + 4) + 8 * entries         # SURVEY.md 8(d): N*(24 + 4 + 8*nbar)
+    return {
+        "roofline": rl[dominant],
+        "roofline_model_energy": rl["k_model_energy"],     # the kernel of configs[1] itself, whichever dominates the step
+        "kernels": {
+            "k_model_energy": {"avg_ms": ms_full, "interactions_per_launch": i_full,
+                               "interactions_per_s": i_full / (ms_full * 1e-3),
+                               "algorithmic_GBps": bytes_full / (ms_full * 1e-3) / 1e9,
+                               "atoms_per_s": W * N_MOL / (ms_full * 1e-3),
+                               "note": "inside the step: the evaluation + every molecule's moments for the step's move kernel "
+                                       "(80 B per molecule written); `plain_avg_ms` is the evaluation alone, timed after the step loop",
+                               "plain_avg_ms": ms_full_plain, "plain_interactions_per_s": i_full / (ms_full_plain * 1e-3),
+                               "plain_algorithmic_GBps": bytes_full / (ms_full_plain * 1e-3) / 1e9},
+            "k_move_energy": {"avg_ms": ms_moves, "interactions_per_launch": i_moves,
+                              "interactions_per_s": i_moves / (ms_moves * 1e-3),
+                              "algorithmic_GBps": bytes_moves / (ms_moves * 1e-3) / 1e9,
+                              "evaluations_per_s": 2 * W * M / (ms_moves * 1e-3)},
+            "k_build_neighbours": {"ms_for_all_walkers": list_ms, "first_build_ms": list_cold_ms, "nn_min": mn, "nn_max": mx,
+                                   "algorithmic_GBps": entries_bytes / (list_ms * 1e-3) / 1e9,
+                                   "convention_frac": entries_bytes / (list_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
+        },
+        "walker0_rel_err_vs_golden": sanity,
+        "walker0_moves_max_rel_err": moves_err, "walker0_moves_checked": n_gold,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -546,7 +653,12 @@ def main():
     ap.add_argument("--walkers", type=int, default=512, help="independent 4096-molecule walkers per GPU")
     ap.add_argument("--moves", type=int, default=2048, help="trial moves per walker per step")
     ap.add_argument("--sigma", type=float, default=0.15)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: CPU baseline, per-kernel and roofline figures, self-checks, "
+                         "secondary and production-driver measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--cpu-worker", action="store_true", help=argparse.SUPPRESS)   # one process of the all-cores CPU leg
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -554,7 +666,8 @@ def main():
     ap.add_argument("--share-device", action="store_true",
                     help="rehearsal on a one-GPU box: every rank computes on device 0 (use with --backend gloo)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary measurements (configs[2] 1536 LS pairs, configs[4] 32768 boxes) after the timed run")
+                    help="--full without the secondary measurements (configs[2] 1536 LS pairs, configs[4] 32768 boxes) and the "
+                         "production-driver measurements after the timed run")
     ap.add_argument("--no-exchange", action="store_true",
                     help="N = 1 only: skip the per-step weight/histogram all-reduce (by default a one-rank process group "
                          "is created so that the N = 1 line times the same step as the N > 1 lines)")
@@ -575,6 +688,8 @@ def main():
         return
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     # Rank / size bootstrap (what comms_initialise does with MPI_Comm_rank / _size, comms_mpi.f90:26-71): the launcher's
     # environment if there is one -- it must then agree with --gpus -- otherwise this process IS the launcher.
     if "WORLD_SIZE" not in os.environ:
@@ -587,7 +702,8 @@ def main():
             raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: start one rank per GPU "
                              f"(python bench.py --gpus {args.gpus} launches them itself when WORLD_SIZE is unset)")
     all_cores = None
-    if world == 1 and not args.no_cpu_baseline:
+    cpu_leg = args.full and world == 1 and not args.no_cpu_baseline
+    if cpu_leg:
         all_cores = cpu_all_cores(args)       # before this process initialises the GPU
 
     import torch
@@ -637,7 +753,8 @@ def main():
     mn, mx = em.build_neighbours_batch(1, W)
     em.timer_stop(4000)
     list_cold_ms = em.timer_ms(4000)                    # the very first launches of the process, GPU at its idle clock
-    list_ms = timed(em, 4001, lambda: em.build_neighbours_launch(1, W), 10)      # steady state: what a farm pays every list_update_int cycles
+    if args.full:                                       # steady state: what a farm pays every list_update_int cycles
+        list_ms = timed(em, 4001, lambda: em.build_neighbours_launch(1, W), 10)
     # trial moves, walker-major
     ils = np.repeat(np.arange(1, W + 1, dtype=np.int32), M)
     imol = np.empty(W * M, dtype=np.int32)
@@ -687,6 +804,7 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if exchange and args.full:
         # every walker of every rank must have ended with the same shared weights / histograms
         chk = torch.tensor(np.concatenate([weight, hist, uhist]), dtype=torch.float64,
                            device="cuda" if args.backend == "nccl" else "cpu")
@@ -704,58 +822,11 @@ def main():
     i_full = npairs + ntrip
     io, so, inw, sn = em.moves_counts()
     i_moves = io + inw
-    entries = em.neighbour_total(1, W)
-    bytes_full = W * N_MOL * (24 + 8) + 8 * entries             # N*(24 + 8*nbar + 8)
-    bytes_moves = 24 * (2 * W * M) + 32 * (so + sn)             # 24 + 8*slots + 24*slots per evaluation
-    nk = min(args.steps, 2000)
-    ms_full = float(np.mean([em.timer_ms(2 * k) for k in range(nk)]))
-    ms_moves = float(np.mean([em.timer_ms(2 * k + 1) for k in range(nk)]))
-    e_walker0 = em.model_energy_fetch(1, 1)[0]
-    # The step's full-box launch also leaves every molecule's moments behind for the step's move kernel (its moment path, DESIGN.md
-    # 3.2): ~50 us of stores on top of the evaluation.  The kernel of configs[1] by itself -- compute_model_energy of every walker,
-    # nothing else -- is timed here, outside the step loop, and is what `roofline_model_energy` describes.
-    for k in range(24):                              # one event pair per launch, each launch behind a launch of the move kernels -- the
-        em.moves_launch()                            # conditions the kernel has inside a step (a bracket of back-to-back launches lets their
-        em.timer_start(4010 + k)                     # tails and heads overlap: 7 % less per launch; launches on an idle GPU: 8 % more)
-        em.model_energy_launch(1, W)
-        em.timer_stop(4010 + k)
-    ms_full_plain = float(np.mean([em.timer_ms(4010 + k) for k in range(4, 24)]))
-    moves_err = None
-    if gold is not None and n_gold:    # what the LAST timed k_move_energy launch left on the device, against the reference's values
+    if args.dump_outputs and rank == 0:      # before anything below launches a kernel again
         eo, en = em.moves_fetch()
-        moves_err = float(max(np.max(np.abs(eo[:n_gold] - gold["trial_old"][:n_gold]) / np.abs(gold["trial_old"][:n_gold])),
-                              np.max(np.abs(en[:n_gold] - gold["trial_new"][:n_gold]) / np.abs(gold["trial_new"][:n_gold]))))
-        if not moves_err <= 1e-10:
-            raise SystemExit(f"walker 0: old/new local energies of the timed move kernel differ from the golden vector (max rel {moves_err:.3e})")
+        dump_outputs(args.dump_outputs, em.model_energy_fetch(1, W), eo, en, (npairs, ntrip, io, inw))
     name, cus, mem = em.device_info()
-
-    # the ceiling a plain device-to-device copy reaches on this box (report against nominal AND this)
-    copy_gbs = None
     if rank == 0:
-        nbytes = 1 << 30
-        a = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-        b = torch.empty_like(a)
-        b.copy_(a); torch.cuda.synchronize()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(10):
-            b.copy_(a)
-        t1.record(); torch.cuda.synchronize()
-        copy_gbs = 2.0 * nbytes * 10 / (t0.elapsed_time(t1) * 1e-3) / 1e9          # bytes read + bytes written
-        del a, b
-
-    if rank == 0:
-        sanity = None
-        if gold is not None:
-            ref = float(gold["model_energy"])
-            sanity = abs(e_walker0 - ref) / abs(ref)
-            if sanity > 1e-10:
-                raise SystemExit(f"walker 0 energy {e_walker0!r} differs from the golden vector {ref!r}")
-        dominant = "k_model_energy" if ms_full >= ms_moves else "k_move_energy"
-        counters = load_counters(W, M)
-        rl = {"k_model_energy": kernel_roofline("k_model_energy", bytes_full, ms_full_plain, W * N_MOL, counters, copy_gbs),
-              "k_move_energy": kernel_roofline("k_move_energy", bytes_moves, ms_moves, W * M, counters, copy_gbs)}
-        entries_bytes = W * N_MOL * (24 + 4) + 8 * entries         # N*(24 + 4 + 8*nbar)
         out = {
             "metric": "mW interactions/sec/GPU (full-box + single-move ΔE), 4096-mol ice; 1/2/4/8-GPU replica scaling",
             "value": (i_full + i_moves) * args.steps * world / elapsed,
@@ -763,7 +834,7 @@ def main():
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
+            "dtype": "f64", "data": "synthetic", "full": args.full,
             "config": {
                 "workload": "ih4096_t015: 4096-molecule ice-Ih boxes (8x8x8 x 8-atom cell, sigma 0.15 A), "
                             "per step: full-box energy of every walker + old/new local energy of every trial move",
@@ -774,38 +845,21 @@ def main():
                             else (exchange_note or "none at N=1 (--no-exchange)"),
             },
             "per_gpu": (i_full + i_moves) * args.steps / elapsed,
-            "roofline": rl[dominant],
-            "roofline_model_energy": rl["k_model_energy"],     # the kernel of configs[1] itself, whichever dominates the step
-            "kernels": {
-                "k_model_energy": {"avg_ms": ms_full, "interactions_per_launch": i_full,
-                                   "interactions_per_s": i_full / (ms_full * 1e-3),
-                                   "algorithmic_GBps": bytes_full / (ms_full * 1e-3) / 1e9,
-                                   "atoms_per_s": W * N_MOL / (ms_full * 1e-3),
-                                   "note": "inside the step: the evaluation + every molecule's moments for the step's move kernel "
-                                           "(80 B per molecule written); `plain_avg_ms` is the evaluation alone, timed after the step loop",
-                                   "plain_avg_ms": ms_full_plain, "plain_interactions_per_s": i_full / (ms_full_plain * 1e-3),
-                                   "plain_algorithmic_GBps": bytes_full / (ms_full_plain * 1e-3) / 1e9},
-                "k_move_energy": {"avg_ms": ms_moves, "interactions_per_launch": i_moves,
-                                   "interactions_per_s": i_moves / (ms_moves * 1e-3),
-                                   "algorithmic_GBps": bytes_moves / (ms_moves * 1e-3) / 1e9,
-                                   "evaluations_per_s": 2 * W * M / (ms_moves * 1e-3)},
-                "k_build_neighbours": {"ms_for_all_walkers": list_ms, "first_build_ms": list_cold_ms, "nn_min": mn, "nn_max": mx,
-                                       "algorithmic_GBps": entries_bytes / (list_ms * 1e-3) / 1e9,
-                                       "convention_frac": entries_bytes / (list_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
-            },
             "device": {"name": name, "compute_units": cus, "hbm_bytes": mem},
-            "walker0_rel_err_vs_golden": sanity,
-            "walker0_moves_max_rel_err": moves_err, "walker0_moves_checked": n_gold,
             "setup_s": t_setup,
         }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(h, xs[0], M, args.cpu_budget)
-            out["cpu_baseline"]["all_cores"] = all_cores
-        else:
-            out["cpu_baseline"] = None
+    if args.full:
+        full = full_measurements(args, em, rank, W, M, gold, n_gold, i_full, i_moves, so, sn, list_cold_ms, list_ms, mn, mx)
+        if rank == 0:
+            out.update(full)
+            if cpu_leg:
+                out["cpu_baseline"] = cpu_baseline(h, xs[0], M, args.cpu_budget)
+                out["cpu_baseline"]["all_cores"] = all_cores
+            else:
+                out["cpu_baseline"] = None
     em.energy_deinit()
     if rank == 0:
-        if not args.no_secondary and world == 1:
+        if args.full and not args.no_secondary and world == 1:
             out["secondary"] = secondary_measurements(local_rank)
             out["production_driver"] = production_driver_measurements(local_rank, args.backend if exchange else "none")
             out["walker0_chain_checked"] = out["production_driver"]["walker0_chain_checked"]

@@ -59,3 +59,53 @@ def list_digest(nn, jn, vn):
 def c_oracle():
     from oracle import COracle
     return COracle()
+
+
+#: what the reference program's runs in the pin tests wrote (oracle/_ref/mc_water_ref_rng*): recorded where the reference's
+#: sources are at hand and oracle/_ref/ is built (MW_RECORD_REF_RUNS=1), replayed everywhere else
+REF_RUNS = os.path.join(GOLDEN, "ref_runs")
+
+
+def _file_digests(d):
+    import hashlib
+    return {n: hashlib.sha256(open(os.path.join(d, n), "rb").read()).hexdigest()
+            for n in sorted(os.listdir(d)) if os.path.isfile(os.path.join(d, n))}
+
+
+def _ref_run_path(binary, args, before, env):
+    """A run is keyed by the program, its arguments, the files of its working directory and the interposition switches."""
+    import hashlib
+    m = hashlib.sha256()
+    for part in [os.path.basename(binary), *args, *(f"{n}:{h}" for n, h in before.items()),
+                 *(f"{k}={env[k]}" for k in sorted(env) if k.startswith("MW_WRAP_"))]:
+        m.update(part.encode() + b"\0")
+    return os.path.join(REF_RUNS, f"{os.path.basename(binary)}_{m.hexdigest()[:20]}.npz")
+
+
+def run_reference_program(binary, args, cwd, env=None, timeout=600):
+    """subprocess.run([binary, *args], cwd=cwd, ...) for a reference program under oracle/_ref/.  Where it is not built (its
+    recipe needs the reference's sources), the recorded run with the same inputs writes its files into `cwd` instead; a run
+    that was never recorded skips the test."""
+    import subprocess
+    env = dict(os.environ if env is None else env)
+    before = _file_digests(cwd)
+    path = _ref_run_path(binary, args, before, env)
+    if not os.path.exists(binary):
+        if not os.path.exists(path):
+            pytest.skip(f"oracle/_ref/{os.path.basename(binary)} not built and this run of it not recorded under tests/golden/ref_runs")
+        z = np.load(path)
+        for k in z.files:
+            if k.startswith("file:"):
+                with open(os.path.join(cwd, k[5:]), "wb") as fh:
+                    fh.write(z[k].tobytes())
+        return subprocess.CompletedProcess([binary, *args], int(z["returncode"]), z["stdout"].tobytes().decode(),
+                                           z["stderr"].tobytes().decode())
+    out = subprocess.run([binary, *args], cwd=cwd, capture_output=True, text=True, timeout=timeout, env=env)
+    if os.environ.get("MW_RECORD_REF_RUNS") == "1" and out.returncode == 0:
+        after = _file_digests(cwd)
+        files = {"file:" + n: np.frombuffer(open(os.path.join(cwd, n), "rb").read(), dtype=np.uint8)
+                 for n, h in after.items() if before.get(n) != h}
+        os.makedirs(REF_RUNS, exist_ok=True)
+        np.savez_compressed(path, returncode=np.int32(out.returncode), stdout=np.frombuffer(out.stdout.encode(), dtype=np.uint8),
+                            stderr=np.frombuffer(out.stderr.encode(), dtype=np.uint8), **files)
+    return out

@@ -42,7 +42,7 @@ def test_two_rank_farm_agrees_on_the_synchronised_tables():
 
 def test_two_rank_bench_line():
     res = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--walkers", "32",
-                   "--moves", "256", "--backend", "gloo", "--share-device", "--no-cpu-baseline"])
+                   "--moves", "256", "--backend", "gloo", "--share-device", "--no-cpu-baseline", "--full"])
     assert res["n_gpus"] == 2 and res["steps"] == 3 and res["scaling"] == "weak" and res["unit"] == "interactions/s"
     assert res["value"] > res["per_gpu"] > 0
     assert res["roofline"]["kernel"] in ("k_move_energy", "k_model_energy") and res["cpu_baseline"] is None

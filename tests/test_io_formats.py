@@ -2,15 +2,15 @@
 restart of the reference program from a checkpoint written by us."""
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from conftest import GOLDEN, REF_RUNS, ROOT, run_reference_program
 
 RNG = os.path.join(ROOT, "oracle", "_ref", "mc_water_ref_rng")
-pytestmark = pytest.mark.skipif(not os.path.exists(RNG), reason="oracle/_ref/mc_water_ref_rng not built")
+needs_ref = pytest.mark.skipif(not (os.path.exists(RNG) or os.path.isdir(REF_RUNS)),
+                               reason="oracle/_ref/mc_water_ref_rng not built and no recorded runs")
 
 
 def _run(d, cycles, weight_grid=None, samplerun=False):
@@ -19,6 +19,7 @@ def _run(d, cycles, weight_grid=None, samplerun=False):
     return P.run_reference(d, 2, 200, cycles, samplerun=samplerun, always_switch=True, tables=True)
 
 
+@needs_ref
 def test_checkpoint_roundtrip_is_byte_identical(tmp_path):
     from mc_water_ls_mw_amd import io as mwio
     d = str(tmp_path / "run")
@@ -32,6 +33,7 @@ def test_checkpoint_roundtrip_is_byte_identical(tmp_path):
     assert open(out, "rb").read() == open(path, "rb").read()
 
 
+@needs_ref
 def test_reference_restarts_from_our_checkpoint(tmp_path):
     """40 cycles in one go == 20 cycles, checkpoint re-written by write_checkpoint, restart for 20 more."""
     import test_sweep_pin as P
@@ -48,8 +50,7 @@ def test_reference_restarts_from_our_checkpoint(tmp_path):
     open(os.path.join(d, "ice.input"), "w").write(nl)
     # the restarted run draws moves 960.. of the same stream only if its wrapper starts there: it does not (the counter
     # restarts at 0), so compare what a restart must preserve exactly: it LOADS our file and continues from cycle 20
-    out = subprocess.run([RNG, "ice.input"], cwd=d, capture_output=True, text=True, timeout=300,
-                         env=dict(os.environ, MW_WRAP_SWITCH="1", MW_WRAP_TRANSP="1.0"))
+    out = run_reference_program(RNG, ["ice.input"], d, env=dict(os.environ, MW_WRAP_SWITCH="1", MW_WRAP_TRANSP="1.0"), timeout=300)
     assert out.returncode == 0, out.stderr[-500:]
     _, c2 = mwio.latest_checkpoint(d)
     assert c2["cycle"] == 40                                    # continued from our cycle 20 for 20 more
@@ -65,7 +66,6 @@ def test_table_files(tmp_path):
     mwio.write_table(p, 0.05, g.mu_bin, w)
     wl, mu, val = mwio.read_table(p)
     assert wl == pytest.approx(0.05) and np.array_equal(mu, g.mu_bin) and np.array_equal(val, w)
-    ref = os.path.join("/root/reference/examples/ice1_sample/eta_weights.dat")
-    if os.path.exists(ref):                                     # the reference's own shipped table parses
-        wl, mu, val = mwio.read_table(ref)
-        assert len(mu) == 101 and wl == pytest.approx(0.05, rel=1e-6) and np.all(np.diff(mu) > 0)
+    # the reference's own shipped table (examples/ice1_sample/eta_weights.dat, stored as a fixture) parses
+    wl, mu, val = mwio.read_table(os.path.join(GOLDEN, "ice1_sample_eta_weights.dat"))
+    assert len(mu) == 101 and wl == pytest.approx(0.05, rel=1e-6) and np.all(np.diff(mu) > 0)

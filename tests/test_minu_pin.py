@@ -12,7 +12,8 @@ import pytest
 import test_sweep_pin as pin
 
 MINU = os.path.join(pin.ROOT, "oracle", "_ref", "mc_water_ref_rng_minu")
-pytestmark = pytest.mark.skipif(not os.path.exists(MINU), reason="oracle/_ref/mc_water_ref_rng_minu not built")
+pytestmark = pytest.mark.skipif(not (os.path.exists(MINU) or os.path.isdir(pin.REF_RUNS)),
+                                reason="oracle/_ref/mc_water_ref_rng_minu not built and no recorded runs")
 
 F0 = float(np.float32(0.05))     # userparams.f90:32: a single-precision literal
 

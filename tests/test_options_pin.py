@@ -19,7 +19,8 @@ import pytest
 
 import test_sweep_pin as pin
 
-pytestmark = pytest.mark.skipif(not os.path.exists(pin.RNG), reason="oracle/_ref/mc_water_ref_rng not built")
+pytestmark = pytest.mark.skipif(not (os.path.exists(pin.RNG) or os.path.isdir(pin.REF_RUNS)),
+                                reason="oracle/_ref/mc_water_ref_rng not built and no recorded runs")
 
 F0 = float(np.float32(0.05))     # userparams.f90:32: a single-precision literal
 

@@ -16,7 +16,8 @@ from conftest import ROOT
 
 import test_sweep_pin as pin
 
-needs_ref = pytest.mark.skipif(not os.path.exists(pin.RNG), reason="oracle/_ref/mc_water_ref_rng not built")
+needs_ref = pytest.mark.skipif(not (os.path.exists(pin.RNG) or os.path.isdir(pin.REF_RUNS)),
+                               reason="oracle/_ref/mc_water_ref_rng not built and no recorded runs")
 
 
 @pytest.fixture(scope="module")

@@ -10,19 +10,19 @@ double precision) having passed through the same energies (thermo file, 6 digits
 two-lattice Ic/Ih system with interpolated multicanonical weights (eta_weights.dat)."""
 import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, load_golden
+from conftest import REF_RUNS, ROOT, load_golden, run_reference_program
 
 RNG = os.path.join(ROOT, "oracle", "_ref", "mc_water_ref_rng")
 SEED = 424242          # oracle/ref_wrap_rng.c
 HART_TO_EV = 27.211396181
 AUP_TO_ATM = 2.90363081e8
 
-pytestmark = pytest.mark.skipif(not os.path.exists(RNG), reason="oracle/_ref/mc_water_ref_rng not built")
+pytestmark = pytest.mark.skipif(not (os.path.exists(RNG) or os.path.isdir(REF_RUNS)),
+                                reason="oracle/_ref/mc_water_ref_rng not built and no recorded runs")
 
 
 def namelist(num_lattices, temperature, cycles, samplerun, always_switch=False, npt=False, vol_prob=None, latt_sync=None,
@@ -101,7 +101,7 @@ def run_reference(d, num_lattices, temperature, cycles, weight=None, grid=None, 
             for mu, w in zip(grid.mu_bin, weight):
                 fh.write(f"  {float(mu)!r}        {float(w)!r}\n")
     env = dict(os.environ, MW_WRAP_SWITCH="1" if always_switch else "0", MW_WRAP_TRANSP=repr(float(transP)), **run_env)
-    out = subprocess.run([program or RNG, "ice.input"], cwd=d, capture_output=True, text=True, timeout=600, env=env)
+    out = run_reference_program(program or RNG, ["ice.input"], d, env=env)
     assert out.returncode == 0, (out.stdout[-800:], out.stderr[-800:])
     therm = [f for f in os.listdir(d) if f.endswith("_therm.dat")][0]
     e_ev = np.array([float(ln.split()[1]) for ln in open(os.path.join(d, therm))])

@@ -5,7 +5,7 @@
 TAG=$1
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out
-python3 bench.py > $O/${TAG}_bench_with_cpu_baseline.json 2> $O/${TAG}_bench.err
+python3 bench.py --full > $O/${TAG}_bench_with_cpu_baseline.json 2> $O/${TAG}_bench.err
 python3 tools/extra_measurements.py > $O/${TAG}_single_call_latency.json 2> $O/${TAG}_extra.err
 python3 tools/dump_workload.py /tmp/wl.bin --walkers 64 --moves 256 > /dev/null 2>&1 && ./tools/kbench /tmp/wl.bin 3 latency > $O/${TAG}_kbench_latency.txt 2>&1
 MW_LOCAL_SERVER=0 ./tools/kbench /tmp/wl.bin 3 latency >> $O/${TAG}_kbench_latency.txt 2>&1

@@ -7,7 +7,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp
-rocprofv3 --pmc $CTR --output-format csv -d $OUT -o pmc -- python3 $REPO/bench.py --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/err.log
+rocprofv3 --pmc $CTR --output-format csv -d $OUT -o pmc -- python3 $REPO/bench.py --full --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/err.log
 python3 - "$OUT" <<'PY'
 import csv, sys, collections, glob
 rows = list(csv.DictReader(open(glob.glob(sys.argv[1] + "/*counter_collection.csv")[0])))

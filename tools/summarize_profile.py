@@ -37,7 +37,7 @@ bench = json.loads(open(os.path.join(src, "bench_trace.json")).read().strip().sp
 W, M = bench["config"]["walkers_per_gpu"], bench["config"]["moves_per_walker"]
 traffic = {"walkers": W, "moves": M, "tag": tag}
 lines = [f"# rocprofv3 summary `{tag}`", "",
-         f"Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --steps {bench['steps']} --warmup {bench['warmup']}`"
+         f"Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --steps {bench['steps']} --warmup {bench['warmup']}`"
          f" (walkers {W}, moves/walker {M}); PMC in separate `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` runs.", "",
          "| kernel | calls | avg us (rocprof) | avg us (bench HIP events) | FETCH_SIZE KiB | WRITE_SIZE KiB | HBM bytes/launch (2*F+W)*1024 |",
          "|---|---|---|---|---|---|---|"]
