@@ -108,6 +108,22 @@ int mw_model_energy_counts_total(int first_ils, int count, long long *npairs, lo
 /* Sum of nn(imol) over those boxes: the number of list entries a full-box pass reads. */
 int mw_neighbour_total(int first_ils, int count, long long *total_entries);
 
+/* ---- gradient of compute_model_energy: forces and virial (no counterpart in the reference) ---- */
+
+/* Energy, forces and virial of box ils from the mirrored positions and the current list (like mw_model_energy):
+ * *e = model energy, bit for bit what mw_model_energy returns; f = nwater x 3 doubles, F_i = -dE/dr_i in molecule order
+ * (Hartree / bohr); w = 9 doubles, column-major like hmatrix: W_ab = -dE/d(strain_ab) under a homogeneous deformation of
+ * positions and cell (Hartree), so the instantaneous pressure is (N k_B T + tr W / 3) / volume.  Results are deterministic
+ * (no atomics) and do not depend on which other boxes share a launch.  The host's model_energy is not touched. */
+int mw_model_forces(int ils, double *e, double *f, double *w);
+/* The same for boxes first_ils .. first_ils+count-1: one moment launch, one force launch, one copy-back.
+ * e = count doubles, f = count x nwater x 3, w = count x 9. */
+int mw_model_forces_batch(int first_ils, int count, double *e, double *f, double *w);
+/* The launches of mw_model_forces_batch without the copy-back (results stay on the device; mw_sync waits for them).
+ * timer_slot >= 0 brackets them with the event timers: slot timer_slot around the moment pass, timer_slot + 1 around the
+ * force pass and the virial sums (read with mw_timer_elapsed_ms). */
+int mw_model_forces_launch(int first_ils, int count, int timer_slot);
+
 /* ---- compute_local_real_energy(imol, ils) (molint.F90:220-404) ------------------- */
 
 /* Local energy of molecule imol from the mirrored positions. */

@@ -66,6 +66,10 @@ struct Ctx {
     int cu = 0, nsplit_max = 0;
     hipStream_t stream = nullptr;
     double* d_pos = nullptr;
+    double* d_force = nullptr;         // [box][N][3]: forces of the last mw_model_forces* call (allocated on first use)
+    double* d_wpart = nullptr;         // [box][nsplit][9]: its per-workgroup virial partials
+    double* d_virial = nullptr;        // [box][9]: its virials, column-major
+    bool forces_attr = false;          // the LDS-staged force kernel's dynamic LDS limit has been raised
     double* d_mom = nullptr;           // [box][N][kMomStride]: per-molecule moments (k_model_energy's by-product) for the single-move kernel's moment path
     int mom_first = 0, mom_count = 0;  // the boxes whose moments the LAST full-box launch left valid (cleared by everything that may move a molecule)
     int swm_first = 0, swm_count = 0;  // the boxes (1-based first) whose moments in d_mom the Monte Carlo driver keeps current from launch to launch
@@ -394,11 +398,13 @@ Geo model_geo(int count)
     return ge;
 }
 
-int launch_model_energy(int first, int count, bool with_mom = false, bool write_energy = true)
+// mom_global: boxes too large for LDS write their moments too (a build of the global-memory kernel of its own, for the force pass;
+// every other caller takes the moment path only where boxes are staged in LDS)
+int launch_model_energy(int first, int count, bool with_mom = false, bool write_energy = true, bool mom_global = false)
 {
     const Geo ge = model_geo(count);
     double* mom = nullptr;
-    if (with_mom && ge.lds) {
+    if (with_mom && (ge.lds || mom_global)) {
         if (!g.d_mom) HIPCHK(hipMalloc(&g.d_mom, (size_t)g.nbox * g.N * mw::kMomStride * sizeof(double)));
         mom = g.d_mom;
     }
@@ -416,6 +422,10 @@ int launch_model_energy(int first, int count, bool with_mom = false, bool write_
         hipLaunchKernelGGL((mw::k_model_energy<true, 1024, kFullLayout>), grid, dim3(1024), ge.shmem, g.stream, g.d_pos, g.d_ivect,
                            g.d_nivect, g.d_list, g.d_order, g.d_nns, g.d_cmax, g.d_partial, g.d_cpartial, g.d_energy, g.d_counts, g.N, g.S, g.ivcap, box0, ge.nsplit, ge.chunk, count,
                            (double*)nullptr, wen);
+    else if (mom)
+        hipLaunchKernelGGL((mw::k_model_energy<false, 256, kFullLayout, true, true>), grid, dim3(256), ge.shmem, g.stream, g.d_pos, g.d_ivect,
+                           g.d_nivect, g.d_list, g.d_order, g.d_nns, g.d_cmax, g.d_partial, g.d_cpartial, g.d_energy, g.d_counts, g.N, g.S, g.ivcap, box0, ge.nsplit, ge.chunk, count,
+                           mom, wen);
     else
         hipLaunchKernelGGL((mw::k_model_energy<false, 256, kFullLayout, true>), grid, dim3(256), ge.shmem, g.stream, g.d_pos, g.d_ivect,
                            g.d_nivect, g.d_list, g.d_order, g.d_nns, g.d_cmax, g.d_partial, g.d_cpartial, g.d_energy, g.d_counts, g.N, g.S, g.ivcap, box0, ge.nsplit, ge.chunk, count,
@@ -427,6 +437,61 @@ int launch_model_energy(int first, int count, bool with_mom = false, bool write_
                            g.d_energy, g.d_counts, box0, count, ge.nsplit);
         HIPCHK(hipGetLastError());
     }
+    return 0;
+}
+
+// Forces and virials of boxes first .. first+count-1 (mw_forces.hip.h): the moments and energies of the current positions,
+// then the force pass over the same positions and lists, then the fixed-order virial sums.  The force pass's geometry depends
+// on N only: one workgroup of 1024 per box with the box staged in LDS where it fits, else ceil(N / 256) workgroups of 256.
+// timer_slot >= 0: event timers timer_slot (moment pass) and timer_slot + 1 (force pass).
+constexpr int kForceBlockLds = 1024, kForceBlockGlobal = 256;
+int launch_model_forces(int first, int count, int timer_slot)
+{
+    const bool lds = lds_fits(g.N, g.ivcap);
+    const int nsplit = lds ? 1 : (g.N + kForceBlockGlobal - 1) / kForceBlockGlobal;
+    if (!g.d_force) {
+        HIPCHK(hipMalloc(&g.d_force, (size_t)g.nbox * g.N * 3 * sizeof(double)));
+        HIPCHK(hipMalloc(&g.d_virial, (size_t)g.nbox * mw::kVirialStride * sizeof(double)));
+        HIPCHK(hipMalloc(&g.d_wpart, (size_t)g.nbox * ((g.N + kForceBlockGlobal - 1) / kForceBlockGlobal) * mw::kVirialStride * sizeof(double)));
+    }
+    if (!g.forces_attr) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mw::k_model_forces<true, kForceBlockLds, kFullLayout>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget));
+        g.forces_attr = true;
+    }
+    const bool timed = timer_slot >= 0;
+    if (timed) {
+        if (timer_slot + 1 >= kTimerSlots) return fail("mw_model_forces_launch: timer slot %d outside 0..%d", timer_slot, kTimerSlots - 2);
+        for (int s = timer_slot; s <= timer_slot + 1; ++s)
+            if (!g.ev[s][0]) { HIPCHK(hipEventCreate(&g.ev[s][0])); HIPCHK(hipEventCreate(&g.ev[s][1])); }
+        HIPCHK(hipEventRecord(g.ev[timer_slot][0], g.stream));
+    }
+    if (launch_model_energy(first, count, true, true, true)) return 1;
+    if (!g.d_mom) return fail("mw_model_forces: no moment buffer");
+    if (timed) { HIPCHK(hipEventRecord(g.ev[timer_slot][1], g.stream)); HIPCHK(hipEventRecord(g.ev[timer_slot + 1][0], g.stream)); }
+    const int box0 = first - 1;
+    if (lds)
+        hipLaunchKernelGGL((mw::k_model_forces<true, kForceBlockLds, kFullLayout>), dim3(1, count), dim3(kForceBlockLds),
+                           mw::lds_vec_bytes((size_t)g.N) + mw::lds_vec_bytes((size_t)g.ivcap), g.stream, g.d_pos, g.d_ivect, g.d_nivect,
+                           g.d_list, g.d_order, g.d_nns, g.d_mom, g.d_force, g.d_wpart, g.N, g.S, g.ivcap, box0);
+    else
+        hipLaunchKernelGGL((mw::k_model_forces<false, kForceBlockGlobal, kFullLayout>), dim3(nsplit, count), dim3(kForceBlockGlobal),
+                           mw::lds_vec_bytes((size_t)g.ivcap), g.stream, g.d_pos, g.d_ivect, g.d_nivect,
+                           g.d_list, g.d_order, g.d_nns, g.d_mom, g.d_force, g.d_wpart, g.N, g.S, g.ivcap, box0);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(mw::k_sum_virial, dim3(count), dim3(64), 0, g.stream, g.d_wpart, g.d_virial, box0, count, nsplit);
+    HIPCHK(hipGetLastError());
+    if (timed) HIPCHK(hipEventRecord(g.ev[timer_slot + 1][1], g.stream));
+    return 0;
+}
+
+int fetch_model_forces(int first, int count, double* e, double* f, double* w)
+{
+    const size_t b0 = (size_t)(first - 1);
+    if (e) HIPCHK(hipMemcpyAsync(e, g.d_energy + b0, sizeof(double) * count, hipMemcpyDeviceToHost, g.stream));
+    if (f) HIPCHK(hipMemcpyAsync(f, g.d_force + b0 * g.N * 3, sizeof(double) * 3 * g.N * count, hipMemcpyDeviceToHost, g.stream));
+    if (w) HIPCHK(hipMemcpyAsync(w, g.d_virial + b0 * mw::kVirialStride, sizeof(double) * mw::kVirialStride * count, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
     return 0;
 }
 
@@ -545,7 +610,7 @@ void release_all()
                     g.d_nivect, g.d_list, g.d_listm, g.d_nn, g.d_stats, g.d_order, g.d_nns, g.d_cmax, g.d_cin, g.d_grid,
                     g.d_usegrid, g.d_cellid, g.d_shift, g.d_sorted, g.d_wrel, g.d_wpos, g.d_wsh, g.d_ccount, g.d_cstart, g.d_ccursor, g.d_partial,
                     g.d_cpartial, g.d_energy, g.d_counts, g.d_mimol, g.d_mtrial, g.d_meold, g.d_menew, g.d_mcnt, g.d_mperm, g.d_mdecl,
-                    g.d_mwork, g.d_mom, g.d_mtot, g.d_wmom, g.d_pm, g.d_srvmomok};
+                    g.d_mwork, g.d_mom, g.d_mtot, g.d_wmom, g.d_pm, g.d_srvmomok, g.d_force, g.d_wpart, g.d_virial};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (g.ev_srv) { (void)hipEventDestroy(g.ev_srv); g.ev_srv = nullptr; }
     if (g.h_pin) (void)hipHostFree(g.h_pin);
@@ -1085,6 +1150,31 @@ int mw_model_energy_of(int ils, const double* xyz, double* e)
     HIPCHK(hipStreamSynchronize(g.stream));
     *e = g.h_pin[16];
     return 0;
+}
+
+int mw_model_forces_launch(int first_ils, int count, int timer_slot)
+{
+    MW_LOCK;
+    if (check_live() || check_range(first_ils, count)) return 1;
+    return launch_model_forces(first_ils, count, timer_slot);
+}
+
+int mw_model_forces_batch(int first_ils, int count, double* e, double* f, double* w)
+{
+    MW_LOCK;
+    if (check_live() || check_range(first_ils, count)) return 1;
+    if (!e || !f || !w) return fail("mw_model_forces_batch: null pointer");
+    if (launch_model_forces(first_ils, count, -1)) return 1;
+    return fetch_model_forces(first_ils, count, e, f, w);
+}
+
+int mw_model_forces(int ils, double* e, double* f, double* w)
+{
+    MW_LOCK;
+    if (check_live() || check_box(ils)) return 1;
+    if (!e || !f || !w) return fail("mw_model_forces: null pointer");
+    if (launch_model_forces(ils, 1, -1)) return 1;
+    return fetch_model_forces(ils, 1, e, f, w);
 }
 
 int mw_model_energy_counts(int ils, long long* npairs, long long* ntriplets)

@@ -40,6 +40,7 @@ ABI_SYMBOLS = (
     "mw_build_neighbours", "mw_build_neighbours_batch", "mw_get_neighbours",
     "mw_model_energy", "mw_model_energy_of", "mw_model_energy_batch", "mw_model_energy_counts",
     "mw_model_energy_counts_total", "mw_neighbour_total",
+    "mw_model_forces", "mw_model_forces_batch", "mw_model_forces_launch",
     "mw_local_energy", "mw_local_energy_patched", "mw_local_energy_post", "mw_local_energy_collect",
     "mw_local_energy_batch", "mw_delta_energy_batch",
     "mw_moves_upload", "mw_moves_launch", "mw_moves_fetch", "mw_moves_counts",
@@ -258,6 +259,35 @@ class EnergyModule:
         self._chk(self.L.mw_model_energy(ils, ctypes.byref(e)))
         self.model_energy[b] = e.value
         return e.value
+
+    # -- gradient of compute_model_energy (no counterpart in the reference) -------------
+    def compute_forces(self, ils):
+        """(energy, forces [nwater, 3], virial [3, 3]) of lattice ils from the HOST's ljr, mirrored first as
+        compute_model_energy does.  forces = -dE/dr (Hartree / bohr), virial W_ab = -dE/d(strain_ab) (Hartree): the
+        instantaneous pressure is (N k_B T + tr W / 3) / volume.  model_energy is the caller's and is left alone."""
+        self._ils(ils)
+        self._upload(ils)
+        e = ctypes.c_double(0.0)
+        f = np.zeros((self.nwater, 3))
+        w = np.zeros(9)
+        self._chk(self.L.mw_model_forces(ils, ctypes.byref(e), _d(f), _d(w)))
+        return e.value, f, w.reshape(3, 3).T.copy()          # w is column-major: w[a + 3 b] = W_ab
+
+    def forces_batch(self, first_ils=1, count=None):
+        """(energies [count], forces [count, nwater, 3], virials [count, 3, 3]) of ``count`` boxes from the positions and
+        cells the DEVICE holds (after device sweeps those are the authoritative ones), in one launch of each pass."""
+        count = self.num_lattices - first_ils + 1 if count is None else count
+        self._ils(first_ils), self._ils(first_ils + count - 1)
+        e = np.zeros(count)
+        f = np.zeros((count, self.nwater, 3))
+        w = np.zeros((count, 9))
+        self._chk(self.L.mw_model_forces_batch(first_ils, count, _d(e), _d(f), _d(w)))
+        return e, f, np.ascontiguousarray(w.reshape(count, 3, 3).transpose(0, 2, 1))
+
+    def forces_launch(self, first_ils, count, timer_slot=-1):
+        """The two passes of forces_batch, results left on the device; timer_slot >= 0: event timers timer_slot (moment
+        pass) and timer_slot + 1 (force pass)."""
+        self._chk(self.L.mw_model_forces_launch(first_ils, count, timer_slot))
 
     def model_energy_counts(self, ils):
         p, t = ctypes.c_longlong(0), ctypes.c_longlong(0)

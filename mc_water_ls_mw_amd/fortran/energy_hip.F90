@@ -44,6 +44,7 @@ module energy
   public :: maxneigh
   public :: nn,jn,vn
   public :: energy_fetch_neighbours   ! extension: fill nn/jn/vn from the device list
+  public :: compute_model_forces      ! extension: forces and virial of the full-box energy
 
   ! current energy due to the model Hamiltonian (host array, written by callers too)
   real(kind=dp),allocatable,dimension(:),save :: model_energy
@@ -137,6 +138,12 @@ module energy
        real(c_double),intent(in) :: xyz(3,*)
        real(c_double),intent(out) :: e
      end function mw_model_energy_of
+     integer(c_int) function mw_model_forces(ils,e,f,w) bind(C,name="mw_model_forces")
+       import :: c_int,c_double
+       integer(c_int),value :: ils
+       real(c_double),intent(out) :: e
+       real(c_double),intent(out) :: f(3,*),w(3,3)
+     end function mw_model_forces
      integer(c_int) function mw_local_energy_patched(ils,imol,r_imol,imol_prev,r_prev,e) &
           bind(C,name="mw_local_energy_patched")
        import :: c_int,c_double
@@ -396,6 +403,26 @@ contains
     model_energy(ils) = e
     return
   end subroutine compute_model_energy
+
+  subroutine compute_model_forces(ils,force,virial)
+    !------------------------------------------------------------------------------!
+    ! Extension (the reference has no forces): the gradient of compute_model_energy !
+    ! for lattice ils from the host's ljr, mirrored first.  force(:,imol) =         !
+    ! -dE/dr_imol (Hartree/bohr); virial(a,b) = -dE/d(strain_ab) (Hartree), so the   !
+    ! instantaneous pressure is (nwater k_B T + trace(virial)/3) / volume(ils).      !
+    ! model_energy is left as the caller has it.                                     !
+    !------------------------------------------------------------------------------!
+    use model, only : ljr
+    implicit none
+    integer,intent(in) :: ils
+    real(kind=dp),intent(out) :: force(:,:),virial(3,3)
+    real(c_double) :: e
+    call mw_check(mw_upload_positions(int(ils,c_int),ljr(:,1,:,ils)),'compute_model_forces')
+    last_imol(ils) = 0
+    stale(ils) = .false.
+    call mw_check(mw_model_forces(int(ils,c_int),e,force,virial),'compute_model_forces')
+    return
+  end subroutine compute_model_forces
 
   subroutine compute_neighbours(ils)
     !------------------------------------------------------------------------------!

@@ -113,6 +113,7 @@ class WalkerFarm:
             raise ValueError("boxes do not split into walkers")
         self.nwalkers = em.num_lattices // nlat
         self.beta = 1.0 / (KB * temperature)                # mc_moves.F90:998
+        self.temperature = float(temperature)
         self.max_trans = max_trans_ang * ANG_TO_BOHR        # io.f90:165
         self.pressure = pressure_au
         self.grid = grid if grid is not None else MuGrid()
@@ -276,6 +277,18 @@ class WalkerFarm:
         self.em.volume[:] = np.abs(det)
         self.em._stale[:] = [False] * nb                # positions on the device are the authoritative ones here
         return h
+
+    def virial_pressures(self, temperature=None):
+        """Instantaneous virial pressure of every walker's current lattice, (N k_B T + tr W / 3) / V, as (Hartree / bohr^3,
+        atm) arrays of length nwalkers.  From the positions and cells the device holds -- the authoritative ones after sweeps
+        with volume moves (the cells are read back through :meth:`sync_cells`).  ``temperature`` (K): the farm's by default."""
+        temp = self.temperature if temperature is None else float(temperature)
+        self.sync_cells()
+        _, _, w = self.em.forces_batch(1, self.em.num_lattices)
+        ls = np.array([self.state(k + 1)["ls"] for k in range(self.nwalkers)], dtype=np.int64)
+        box = np.arange(self.nwalkers) * self.nlat + (ls - 1)
+        p = (self.em.nwater * KB * temp + np.trace(w[box], axis1=1, axis2=2) / 3.0) / self.em.volume[box]
+        return p, p * 2.90363081e8                                      # a.u. -> atm, as farm.py converts the imposed pressure
 
     # -- chain synchronisation (mc_check_chain_synchronisation, mc_moves.F90:2217-2416) -------------------------
     def set_reference(self):
