@@ -124,6 +124,24 @@ int mw_model_forces_batch(int first_ils, int count, double *e, double *f, double
  * force pass and the virial sums (read with mw_timer_elapsed_ms). */
 int mw_model_forces_launch(int first_ils, int count, int timer_slot);
 
+/* ---- ice structure classes, CHILL+ (no counterpart in the reference) ----------------------------------------------- */
+
+/* Per-molecule class of box ils from the mirrored positions and the current list (like mw_model_energy), with the bond
+ * cutoff rc in bohr, 0 < rc <= a sigma (the SW cutoff, which the list covers): 0 other / liquid, 1 cubic ice, 2 hexagonal
+ * ice, 3 interfacial ice, 4 clathrate, 5 interfacial clathrate (DESIGN.md "Ice structure classes").  cls = nwater bytes in
+ * molecule order, counts = the six class counts; either may be NULL.  Positions, lists, energies and moments are not
+ * touched, and the results do not depend on which other boxes share a launch. */
+int mw_ice_classes(int ils, double rc, uint8_t *cls, int counts[6]);
+/* The same for boxes first_ils .. first_ils+count-1 in one launch of each pass: cls = count x nwater, counts = count x 6. */
+int mw_ice_classes_batch(int first_ils, int count, double rc, uint8_t *cls, int *counts);
+/* The launches of mw_ice_classes_batch without the copy-back (results stay on the device; mw_sync waits for them).
+ * timer_slot >= 0: event timer timer_slot around pass 1 (bond-order vectors), timer_slot + 1 around pass 2 (classes). */
+int mw_ice_classes_launch(int first_ils, int count, double rc, int timer_slot);
+/* The bond value c of every list entry of box ils, in the layout of mw_get_neighbours' jn (maxneigh x nwater, slot
+ * fastest): c = q_i.q_j / (|q_i| |q_j|) for a neighbour entry, NaN where q_i or q_j is degenerate, 1 for an image of i
+ * itself, exactly 2.0 for an entry that is not a bond (unused slot, |d| >= rc or |d| = 0). */
+int mw_ice_bonds(int ils, double rc, double *c);
+
 /* ---- compute_local_real_energy(imol, ils) (molint.F90:220-404) ------------------- */
 
 /* Local energy of molecule imol from the mirrored positions. */

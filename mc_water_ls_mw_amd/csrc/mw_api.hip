@@ -70,6 +70,13 @@ struct Ctx {
     double* d_wpart = nullptr;         // [box][nsplit][9]: its per-workgroup virial partials
     double* d_virial = nullptr;        // [box][9]: its virials, column-major
     bool forces_attr = false;          // the LDS-staged force kernel's dynamic LDS limit has been raised
+    double* d_iceq = nullptr;          // [box][N][kIceQStride]: q^ of the last mw_ice_* call (allocated on first use)
+    int4* d_icenb = nullptr;           // [box][N]: its first four neighbours of every molecule
+    int* d_icen = nullptr;             // [box][N]: its neighbour counts n_i
+    uint8_t* d_icecls = nullptr;       // [box][N]: its classes
+    int* d_icecnt = nullptr;           // [box][kIceClasses]: its class counts
+    double* d_icebond = nullptr;       // [N][S]: the bond values of mw_ice_bonds' box
+    bool ice_attr = false;             // the LDS-staged pass 1's dynamic LDS limit has been raised
     double* d_mom = nullptr;           // [box][N][kMomStride]: per-molecule moments (k_model_energy's by-product) for the single-move kernel's moment path
     int mom_first = 0, mom_count = 0;  // the boxes whose moments the LAST full-box launch left valid (cleared by everything that may move a molecule)
     int swm_first = 0, swm_count = 0;  // the boxes (1-based first) whose moments in d_mom the Monte Carlo driver keeps current from launch to launch
@@ -495,6 +502,69 @@ int fetch_model_forces(int first, int count, double* e, double* f, double* w)
     return 0;
 }
 
+// Ice structure classes of boxes first .. first+count-1 (mw_ice.hip.h) from the mirrored positions and the current lists:
+// pass 1 (k_ice_q) with the geometry of the force pass -- one workgroup of 1024 per box with the box staged in LDS where it
+// fits, else ceil(N / 256) workgroups of 256 -- then pass 2 (k_ice_class), ceil(N / 256) workgroups of 256 per box.
+// timer_slot >= 0: event timers timer_slot (pass 1) and timer_slot + 1 (pass 2).
+constexpr int kIceBlockLds = 1024, kIceBlockGlobal = 256, kIceBlockClass = 256;
+int check_ice_rc(const char* who, double rc)
+{
+    return (rc > 0.0 && rc <= mw::kSigA) ? 0 : fail("%s: r_c = %g bohr outside (0, a sigma = %.6f]", who, rc, mw::kSigA);
+}
+
+int launch_ice_classes(int first, int count, double rc, int timer_slot)
+{
+    const bool lds = lds_fits(g.N, g.ivcap);
+    const int nsplit = lds ? 1 : (g.N + kIceBlockGlobal - 1) / kIceBlockGlobal;
+    if (!g.d_iceq) {
+        const size_t nm = (size_t)g.nbox * g.N;
+        HIPCHK(hipMalloc(&g.d_iceq, nm * mw::kIceQStride * sizeof(double)));
+        HIPCHK(hipMalloc(&g.d_icenb, nm * sizeof(int4)));
+        HIPCHK(hipMalloc(&g.d_icen, nm * sizeof(int)));
+        HIPCHK(hipMalloc(&g.d_icecls, nm * sizeof(uint8_t)));
+        HIPCHK(hipMalloc(&g.d_icecnt, (size_t)g.nbox * mw::kIceClasses * sizeof(int)));
+    }
+    if (!g.ice_attr) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mw::k_ice_q<true, kIceBlockLds, kFullLayout>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget));
+        g.ice_attr = true;
+    }
+    const bool timed = timer_slot >= 0;
+    if (timed) {
+        if (timer_slot + 1 >= kTimerSlots) return fail("mw_ice_classes_launch: timer slot %d outside 0..%d", timer_slot, kTimerSlots - 2);
+        for (int s = timer_slot; s <= timer_slot + 1; ++s)
+            if (!g.ev[s][0]) { HIPCHK(hipEventCreate(&g.ev[s][0])); HIPCHK(hipEventCreate(&g.ev[s][1])); }
+        HIPCHK(hipEventRecord(g.ev[timer_slot][0], g.stream));
+    }
+    const int box0 = first - 1;
+    const double rc2 = rc * rc;
+    if (lds)
+        hipLaunchKernelGGL((mw::k_ice_q<true, kIceBlockLds, kFullLayout>), dim3(1, count), dim3(kIceBlockLds),
+                           mw::lds_vec_bytes((size_t)g.N) + mw::lds_vec_bytes((size_t)g.ivcap), g.stream, g.d_pos, g.d_ivect, g.d_nivect,
+                           g.d_list, g.d_order, g.d_nns, rc2, g.d_iceq, g.d_icenb, g.d_icen, g.d_icecnt, g.N, g.S, g.ivcap, box0);
+    else
+        hipLaunchKernelGGL((mw::k_ice_q<false, kIceBlockGlobal, kFullLayout>), dim3(nsplit, count), dim3(kIceBlockGlobal),
+                           mw::lds_vec_bytes((size_t)g.ivcap), g.stream, g.d_pos, g.d_ivect, g.d_nivect,
+                           g.d_list, g.d_order, g.d_nns, rc2, g.d_iceq, g.d_icenb, g.d_icen, g.d_icecnt, g.N, g.S, g.ivcap, box0);
+    HIPCHK(hipGetLastError());
+    if (timed) { HIPCHK(hipEventRecord(g.ev[timer_slot][1], g.stream)); HIPCHK(hipEventRecord(g.ev[timer_slot + 1][0], g.stream)); }
+    hipLaunchKernelGGL((mw::k_ice_class<kIceBlockClass>), dim3((g.N + kIceBlockClass - 1) / kIceBlockClass, count), dim3(kIceBlockClass), 0,
+                       g.stream, g.d_iceq, g.d_icenb, g.d_icen, g.d_icecls, g.d_icecnt, g.N, box0);
+    HIPCHK(hipGetLastError());
+    if (timed) HIPCHK(hipEventRecord(g.ev[timer_slot + 1][1], g.stream));
+    return 0;
+}
+
+int fetch_ice_classes(int first, int count, uint8_t* cls, int* counts)
+{
+    const size_t b0 = (size_t)(first - 1);
+    if (cls) HIPCHK(hipMemcpyAsync(cls, g.d_icecls + b0 * g.N, (size_t)g.N * count, hipMemcpyDeviceToHost, g.stream));
+    if (counts) HIPCHK(hipMemcpyAsync(counts, g.d_icecnt + b0 * mw::kIceClasses, sizeof(int) * mw::kIceClasses * count,
+                                      hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    return 0;
+}
+
 size_t sort_box_lds_bytes() { return (size_t)g.N * 24 + ((size_t)g.cstride + 1) * 4; }
 
 int launch_build(int first, int count)
@@ -610,7 +680,8 @@ void release_all()
                     g.d_nivect, g.d_list, g.d_listm, g.d_nn, g.d_stats, g.d_order, g.d_nns, g.d_cmax, g.d_cin, g.d_grid,
                     g.d_usegrid, g.d_cellid, g.d_shift, g.d_sorted, g.d_wrel, g.d_wpos, g.d_wsh, g.d_ccount, g.d_cstart, g.d_ccursor, g.d_partial,
                     g.d_cpartial, g.d_energy, g.d_counts, g.d_mimol, g.d_mtrial, g.d_meold, g.d_menew, g.d_mcnt, g.d_mperm, g.d_mdecl,
-                    g.d_mwork, g.d_mom, g.d_mtot, g.d_wmom, g.d_pm, g.d_srvmomok, g.d_force, g.d_wpart, g.d_virial};
+                    g.d_mwork, g.d_mom, g.d_mtot, g.d_wmom, g.d_pm, g.d_srvmomok, g.d_force, g.d_wpart, g.d_virial,
+                    g.d_iceq, g.d_icenb, g.d_icen, g.d_icecls, g.d_icecnt, g.d_icebond};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (g.ev_srv) { (void)hipEventDestroy(g.ev_srv); g.ev_srv = nullptr; }
     if (g.h_pin) (void)hipHostFree(g.h_pin);
@@ -1175,6 +1246,45 @@ int mw_model_forces(int ils, double* e, double* f, double* w)
     if (!e || !f || !w) return fail("mw_model_forces: null pointer");
     if (launch_model_forces(ils, 1, -1)) return 1;
     return fetch_model_forces(ils, 1, e, f, w);
+}
+
+int mw_ice_classes_launch(int first_ils, int count, double rc, int timer_slot)
+{
+    MW_LOCK;
+    if (check_live() || check_range(first_ils, count) || check_ice_rc("mw_ice_classes_launch", rc)) return 1;
+    return launch_ice_classes(first_ils, count, rc, timer_slot);
+}
+
+int mw_ice_classes_batch(int first_ils, int count, double rc, uint8_t* cls, int* counts)
+{
+    MW_LOCK;
+    if (check_live() || check_range(first_ils, count) || check_ice_rc("mw_ice_classes_batch", rc)) return 1;
+    if (launch_ice_classes(first_ils, count, rc, -1)) return 1;
+    return fetch_ice_classes(first_ils, count, cls, counts);
+}
+
+int mw_ice_classes(int ils, double rc, uint8_t* cls, int counts[6])
+{
+    MW_LOCK;
+    if (check_live() || check_box(ils) || check_ice_rc("mw_ice_classes", rc)) return 1;
+    if (launch_ice_classes(ils, 1, rc, -1)) return 1;
+    return fetch_ice_classes(ils, 1, cls, counts);
+}
+
+int mw_ice_bonds(int ils, double rc, double* c)
+{
+    MW_LOCK;
+    if (check_live() || check_box(ils) || check_ice_rc("mw_ice_bonds", rc)) return 1;
+    if (!c) return fail("mw_ice_bonds: null pointer");
+    if (launch_ice_classes(ils, 1, rc, -1)) return 1;
+    const size_t n = (size_t)g.N * g.S;
+    if (!g.d_icebond) HIPCHK(hipMalloc(&g.d_icebond, n * sizeof(double)));
+    hipLaunchKernelGGL(mw::k_ice_bonds, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g.stream, g.d_pos, g.d_ivect, g.d_listm,
+                       g.d_nn, g.d_iceq, rc * rc, g.d_icebond, g.N, g.S, g.ivcap, ils - 1);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c, g.d_icebond, n * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    return 0;
 }
 
 int mw_model_energy_counts(int ils, long long* npairs, long long* ntriplets)

@@ -41,6 +41,7 @@ ABI_SYMBOLS = (
     "mw_model_energy", "mw_model_energy_of", "mw_model_energy_batch", "mw_model_energy_counts",
     "mw_model_energy_counts_total", "mw_neighbour_total",
     "mw_model_forces", "mw_model_forces_batch", "mw_model_forces_launch",
+    "mw_ice_classes", "mw_ice_classes_batch", "mw_ice_classes_launch", "mw_ice_bonds",
     "mw_local_energy", "mw_local_energy_patched", "mw_local_energy_post", "mw_local_energy_collect",
     "mw_local_energy_batch", "mw_delta_energy_batch",
     "mw_moves_upload", "mw_moves_launch", "mw_moves_fetch", "mw_moves_counts",
@@ -110,6 +111,20 @@ def _d(a):
 
 def _i(a):
     return a.ctypes.data_as(_ip)
+
+
+def _u8(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+
+
+#: the classes of mw_ice_classes (CHILL+), by index
+ICE_CLASS_NAMES = ("other", "cubic ice", "hexagonal ice", "interfacial ice", "clathrate", "interfacial clathrate")
+#: the usual CHILL+ bond cutoff for mW, Angstrom
+ICE_RC_ANG = 3.5
+
+
+def _rc(rc_ang):
+    return ctypes.c_double(float(rc_ang) / 0.5291772108)          # Angstrom -> bohr (constants.f90:42-43)
 
 
 class EnergyModule:
@@ -288,6 +303,41 @@ class EnergyModule:
         """The two passes of forces_batch, results left on the device; timer_slot >= 0: event timers timer_slot (moment
         pass) and timer_slot + 1 (force pass)."""
         self._chk(self.L.mw_model_forces_launch(first_ils, count, timer_slot))
+
+    # -- ice structure classes, CHILL+ (no counterpart in the reference) ---------------
+    def ice_classes(self, ils, rc_ang=ICE_RC_ANG):
+        """(classes uint8 [nwater], counts [6]) of lattice ils from the HOST's ljr, mirrored first as compute_model_energy
+        does, on the current list.  Class k is ICE_CLASS_NAMES[k]; ``rc_ang`` is the bond cutoff in Angstrom."""
+        self._ils(ils)
+        self._upload(ils)
+        cls = np.zeros(self.nwater, dtype=np.uint8)
+        counts = np.zeros(6, dtype=np.int32)
+        self._chk(self.L.mw_ice_classes(ils, _rc(rc_ang), _u8(cls), _i(counts)))
+        return cls, counts
+
+    def ice_classes_batch(self, first_ils=1, count=None, rc_ang=ICE_RC_ANG):
+        """(classes [count, nwater], counts [count, 6]) of ``count`` boxes from the positions and cells the DEVICE holds, in
+        one launch of each pass."""
+        count = self.num_lattices - first_ils + 1 if count is None else count
+        self._ils(first_ils), self._ils(first_ils + count - 1)
+        cls = np.zeros((count, self.nwater), dtype=np.uint8)
+        counts = np.zeros((count, 6), dtype=np.int32)
+        self._chk(self.L.mw_ice_classes_batch(first_ils, count, _rc(rc_ang), _u8(cls), _i(counts)))
+        return cls, counts
+
+    def ice_classes_launch(self, first_ils, count, rc_ang=ICE_RC_ANG, timer_slot=-1):
+        """The two passes of ice_classes_batch, results left on the device; timer_slot >= 0: event timers timer_slot (pass 1,
+        bond-order vectors) and timer_slot + 1 (pass 2, classes)."""
+        self._chk(self.L.mw_ice_classes_launch(first_ils, count, _rc(rc_ang), timer_slot))
+
+    def ice_bonds(self, ils, rc_ang=ICE_RC_ANG):
+        """Bond value c of every list entry of lattice ils as [nwater, maxneigh], laid out like ``neighbours(ils)[1]``: 2.0
+        where the entry is not a bond, NaN where it is degenerate.  The host's ljr is mirrored first, as in ice_classes."""
+        self._ils(ils)
+        self._upload(ils)
+        c = np.zeros((self.nwater, self.maxneigh))
+        self._chk(self.L.mw_ice_bonds(ils, _rc(rc_ang), _d(c)))
+        return c
 
     def model_energy_counts(self, ils):
         p, t = ctypes.c_longlong(0), ctypes.c_longlong(0)

@@ -45,6 +45,7 @@ module energy
   public :: nn,jn,vn
   public :: energy_fetch_neighbours   ! extension: fill nn/jn/vn from the device list
   public :: compute_model_forces      ! extension: forces and virial of the full-box energy
+  public :: compute_ice_classes       ! extension: CHILL+ ice structure class of every molecule
 
   ! current energy due to the model Hamiltonian (host array, written by callers too)
   real(kind=dp),allocatable,dimension(:),save :: model_energy
@@ -144,6 +145,13 @@ module energy
        real(c_double),intent(out) :: e
        real(c_double),intent(out) :: f(3,*),w(3,3)
      end function mw_model_forces
+     integer(c_int) function mw_ice_classes(ils,rc,cls,counts) bind(C,name="mw_ice_classes")
+       import :: c_int,c_double,c_int8_t
+       integer(c_int),value :: ils
+       real(c_double),value :: rc
+       integer(c_int8_t),intent(out) :: cls(*)
+       integer(c_int),intent(out) :: counts(6)
+     end function mw_ice_classes
      integer(c_int) function mw_local_energy_patched(ils,imol,r_imol,imol_prev,r_prev,e) &
           bind(C,name="mw_local_energy_patched")
        import :: c_int,c_double
@@ -423,6 +431,27 @@ contains
     call mw_check(mw_model_forces(int(ils,c_int),e,force,virial),'compute_model_forces')
     return
   end subroutine compute_model_forces
+
+  subroutine compute_ice_classes(ils,rc,cls,counts)
+    !------------------------------------------------------------------------------!
+    ! Extension (the reference can only write DCD frames): CHILL+ class of every    !
+    ! molecule of lattice ils from the host's ljr, mirrored first, on the current   !
+    ! list.  rc = bond cutoff in bohr, 0 < rc <= a sigma (3.5 Angstrom is usual).   !
+    ! cls(imol): 0 other, 1 cubic ice, 2 hexagonal ice, 3 interfacial ice,           !
+    ! 4 clathrate, 5 interfacial clathrate; counts(k+1) = molecules of class k.      !
+    !------------------------------------------------------------------------------!
+    use model, only : ljr
+    implicit none
+    integer,intent(in) :: ils
+    real(kind=dp),intent(in) :: rc
+    integer(c_int8_t),intent(out) :: cls(:)
+    integer(c_int),intent(out) :: counts(6)
+    call mw_check(mw_upload_positions(int(ils,c_int),ljr(:,1,:,ils)),'compute_ice_classes')
+    last_imol(ils) = 0
+    stale(ils) = .false.
+    call mw_check(mw_ice_classes(int(ils,c_int),real(rc,c_double),cls,counts),'compute_ice_classes')
+    return
+  end subroutine compute_ice_classes
 
   subroutine compute_neighbours(ils)
     !------------------------------------------------------------------------------!

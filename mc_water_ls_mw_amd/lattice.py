@@ -99,6 +99,39 @@ def ice_ih_cell(d_oo_ang=D_OO_ANG):
     return h * ANG_TO_BOHR, xyz * ANG_TO_BOHR
 
 
+def stacked_ice_box(sequence, reps_xy=(2, 1), sigma_ang=0.0, seed=20250228):
+    """Ice with an arbitrary stacking of bilayers along z: ``sequence`` is a cyclic string over {A, B, C} with no two
+    neighbours equal (the last and the first included).  Bilayer k has its lower sublayer on site ``sequence[k-1]`` and its
+    upper sublayer d/3 above on site ``sequence[k]``; bilayers are 4d/3 apart, so the upper sublayer of bilayer k and the
+    lower one of bilayer k+1 share a site and are bonded along z.  The sites are those of :func:`ice_ih_cell` (A and B; C
+    is the third), the cell is ``reps_xy`` times a x sqrt(3) a in the plane and len(sequence) 4d/3 high.  "AB" / "ABAB"
+    give Ih, "ABC" gives Ic.  Junction k (bilayers k, k+1) is hexagonal iff sequence[k-1] == sequence[k+1], cubic otherwise.
+    Molecules are ordered by bilayer, then sublayer, then in-plane replica.  Returns ``(h, xyz)`` in bohr."""
+    seq = str(sequence)
+    n = len(seq)
+    if n < 2 or any(s not in "ABC" for s in seq) or any(seq[k] == seq[(k + 1) % n] for k in range(n)):
+        raise ValueError(f"stacking sequence {sequence!r}: needs at least two letters of A, B, C, cyclically no two neighbours equal")
+    d = D_OO_ANG
+    a = d * np.sqrt(8.0 / 3.0)
+    b = np.sqrt(3.0) * a
+    # the two in-plane sites per a x b cell of each stacking position (ice_ih_cell: A = p1, B = p2, each + (a/2, b/2))
+    site = {"A": np.array([[0.0, b / 3.0], [a / 2.0, 5.0 * b / 6.0]]),
+            "B": np.array([[a / 2.0, b / 6.0], [0.0, 2.0 * b / 3.0]]),
+            "C": np.array([[0.0, 0.0], [a / 2.0, b / 2.0]])}
+    nx, ny = reps_xy
+    shifts = np.array([[i * a, j * b] for i in range(nx) for j in range(ny)])
+    out = []
+    for k in range(n):
+        for s, z in ((seq[k - 1], k * 4.0 * d / 3.0), (seq[k], k * 4.0 * d / 3.0 + d / 3.0)):
+            xy = (shifts[:, None, :] + site[s][None, :, :]).reshape(-1, 2)
+            out.append(np.column_stack([xy, np.full(len(xy), z)]))
+    h = np.diag([nx * a, ny * b, n * 4.0 * d / 3.0]) * ANG_TO_BOHR
+    xyz = np.ascontiguousarray(np.concatenate(out, axis=0) * ANG_TO_BOHR)
+    if sigma_ang > 0.0:
+        xyz = thermalise(xyz, sigma_ang, seed)
+    return h, xyz
+
+
 def ice_box(kind, reps, sigma_ang=0.0, seed=20250228):
     """Synthetic ice box: ``kind`` in {"ih","ic"}, ``reps`` replicas of the 8-atom
     cell, optional Gaussian thermal displacement (Angstrom) with a fixed seed."""

@@ -290,6 +290,16 @@ class WalkerFarm:
         p = (self.em.nwater * KB * temp + np.trace(w[box], axis1=1, axis2=2) / 3.0) / self.em.volume[box]
         return p, p * 2.90363081e8                                      # a.u. -> atm, as farm.py converts the imposed pressure
 
+    def ice_fractions(self, rc_ang=3.5):
+        """CHILL+ class fractions of every lattice of every walker, (nwalkers, nlat, 6) with class k as
+        energy.ICE_CLASS_NAMES[k], from the positions and cells the device holds (the cells read back through
+        :meth:`sync_cells` first).  The lattice-switch validity check: each lattice of a walker must stay the crystal it
+        is labelled as (all hexagonal, or all cubic) -- a melted or restacked lattice makes the free-energy difference
+        meaningless."""
+        self.sync_cells()
+        _, counts = self.em.ice_classes_batch(1, self.em.num_lattices, rc_ang)
+        return counts.reshape(self.nwalkers, self.nlat, 6) / float(self.em.nwater)
+
     # -- chain synchronisation (mc_check_chain_synchronisation, mc_moves.F90:2217-2416) -------------------------
     def set_reference(self):
         """Remember the reference configuration (ref_hmatrix / ref_ljr of init.f90:90,106) from the host's current
