@@ -35,6 +35,24 @@ extern "C" {
 #define MW_MAXNEIGH_LIMIT 64   /* the per-atom in-range mask is one 64-bit word        */
 #define MW_MAX_IVECT      1024 /* 10 bits of a packed list entry hold the image number */
 
+/* kernel families of mw_last_dispatch, and the most fields it reports for one */
+#define MW_DISPATCH_BUILD    0
+#define MW_DISPATCH_ENERGY   1
+#define MW_DISPATCH_MOVES    2
+#define MW_DISPATCH_FORCES   3
+#define MW_DISPATCH_ICE      4
+#define MW_DISPATCH_FAMILIES 5
+#define MW_DISPATCH_FIELDS   10
+
+/* LDS-staged builds of mw_lds_plan */
+#define MW_LDS_ENERGY 0        /* k_model_energy, box staged in LDS (both MOMOUT builds)              */
+#define MW_LDS_FORCES 1        /* k_model_forces, box staged in LDS                                   */
+#define MW_LDS_ICE    2        /* k_ice_q, box staged in LDS                                          */
+#define MW_LDS_MOVE   3        /* k_move_energy, box staged in LDS (all three builds), largest item   */
+#define MW_LDS_SORT   4        /* k_cell_sort_box: bin + scan + scatter of a box in one workgroup     */
+#define MW_LDS_ORDER  5        /* k_list_order over the whole box as one segment                      */
+#define MW_LDS_BUILDS 6
+
 /* ---- lifetime: energy_init / energy_deinit (molint.F90:91-153, 155-171) ---------- */
 
 /* Allocate device state for `nboxes` boxes of `nwater` molecules each with
@@ -302,6 +320,27 @@ int mw_sweep_last_launch(int *nlat, int *ahead, int *residency, int *volume_move
  * volume moves -- mw_sweep_moves keeps room for one more shell of images than a 27-image cell has).  Returns -1 for
  * arguments no launch would use. */
 int mw_sweep_lds_bytes(int nlat, int nwater, int nbins, int row_stride, int volume_moves, int samplerun, int image_capacity);
+
+/* ---- which build a launch took (diagnostics; no counterpart in the reference) ---- */
+
+/* What the last launch of kernel family `family` (MW_DISPATCH_*) did, as up to MW_DISPATCH_FIELDS ints; field 0 is always the
+ * image-vector capacity (ivcap) in effect.  Fails before the first launch of that family.
+ *   BUILD  : ivcap, boxes, boxes through the cell grid, boxes through the brute-force kernel, fused LDS sort (k_cell_sort_box)
+ *            rather than bin / scan / scatter, legacy one-thread-per-molecule search, k_list_order segment, segments per box,
+ *            k_list_order dynamic LDS
+ *   ENERGY : ivcap, boxes, box staged in LDS, workgroups per box (nsplit), molecules per workgroup (chunk), grid.y (fewer than
+ *            the boxes: persistent workgroups), moments written, dynamic LDS, workgroup size
+ *   MOVES  : ivcap, requests, box staged in LDS (mlds), no self-images (m_noself), moment path, moments taken from the last
+ *            full-box pass (fresh), requests per work item (mchunk), work items, dynamic LDS, build (0 L2 gather, 1 LDS with
+ *            self-images, 2 LDS without, 3 moment path)
+ *   FORCES, ICE : ivcap, boxes, box staged in LDS, workgroups per box, dynamic LDS
+ * The full-box family also reports the moment passes that the move, force and driver launches run for themselves. */
+int mw_last_dispatch(int family, int *fields, int nfields);
+/* For `nwater` molecules and `image_capacity` image vectors per box, out[2 k] = whether LDS build k (MW_LDS_*) is admitted and
+ * out[2 k + 1] = the dynamic LDS (bytes) it asks for (MW_LDS_MOVE: with the largest work item) -- the launches' own rules,
+ * host arithmetic only, no device needed.  Writes min(nout, 2 MW_LDS_BUILDS) ints; returns MW_LDS_BUILDS, or -1 for
+ * arguments no engine would use. */
+int mw_lds_plan(int nwater, int image_capacity, int *out, int nout);
 
 /* HIP-event timers on the engine's stream: slot in 0..4095. */
 int mw_timer_start(int slot);

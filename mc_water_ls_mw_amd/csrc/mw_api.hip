@@ -108,6 +108,9 @@ struct Ctx {
     std::vector<int> h_usegrid;
     std::vector<char> h_listbuilt;     // per box: a neighbour list has been built (the full-box kernel may be run over it)
     int last_sweep[6] = {0, 0, 0, 0, 0, 0};   // what the last launch of the driver was: lattices, look-ahead, residency, volume moves, LDS bytes, row stride
+    int disp[MW_DISPATCH_FAMILIES][MW_DISPATCH_FIELDS] = {};   // what the last launch of each family did (mw_last_dispatch); field 0 is the ivcap, 0 before any launch
+    int move_moments = -1;             // MW_MOVE_MOMENTS at mw_init: -1 unset (the request-count rule), 0 scanning path, 1 moment path where admitted
+    bool model_persist = true;         // MW_MODEL_PERSIST at mw_init (0: one workgroup per box, A/B only)
     bool grid_on_device = false;   // some box of this context has (had) a cell grid: descriptors travel with mw_sweep_sync_cells
     bool force_brute = false;
     double* d_partial = nullptr;
@@ -237,15 +240,40 @@ struct DeviceGuard {
 constexpr size_t kQueue1024 = (size_t)(mw::kQCap + 1) * 1024 * sizeof(uint32_t);
 constexpr size_t kQueue256 = (size_t)(mw::kQCap + 1) * 256 * sizeof(uint32_t);
 constexpr int kFullLayout = mw::kLayoutPair;      // LDS layout of the full-box kernel's staged vectors (mw_full_energy.hip.h)
+// Dynamic LDS of each LDS-staged build and the rules that admit it: the launches and mw_lds_plan use these and nothing else.
+size_t model_lds_bytes(int N, int ivcap) { return kQueue1024 + mw::lds_vec_bytes((size_t)N) + mw::lds_vec_bytes((size_t)ivcap); }
 bool lds_fits(int N, int ivcap)
 {
-    return kQueue1024 + mw::lds_vec_bytes((size_t)N) + mw::lds_vec_bytes((size_t)ivcap) <= (size_t)kLdsBudget;
+    return model_lds_bytes(N, ivcap) <= (size_t)kLdsBudget;
 }
+size_t pos_lds_bytes(int N, int ivcap) { return mw::lds_vec_bytes((size_t)N) + mw::lds_vec_bytes((size_t)ivcap); }   // force pass, ice pass 1
 constexpr size_t kMoveScratch = 16 * sizeof(mw::WaveScratch);
-constexpr size_t kMoveStage = (size_t)mw::kMoveChunk * sizeof(int);   // the molecules of an item's requests in LDS (at most)
+// (chunk: requests per work item, whose molecules an item keeps in LDS -- at most kMoveChunk)
+size_t move_lds_bytes(int N, int ivcap, int chunk)
+{
+    return kMoveScratch + mw::lds_vec_bytes((size_t)ivcap) + mw::lds_vec_bytes((size_t)N) + (((size_t)N + 7) & ~(size_t)7) + (size_t)chunk * sizeof(int);
+}
 bool lds_fits_move(int N, int ivcap)
 {
-    return kMoveScratch + mw::lds_vec_bytes((size_t)N) + mw::lds_vec_bytes((size_t)ivcap) + (((size_t)N + 7) & ~(size_t)7) + kMoveStage <= (size_t)kLdsBudget;
+    return move_lds_bytes(N, ivcap, mw::kMoveChunk) <= (size_t)kLdsBudget;
+}
+int cell_stride(int N) { return N + 64; }
+size_t sort_lds_bytes(int N) { return (size_t)N * 24 + ((size_t)cell_stride(N) + 1) * 4; }
+bool sort_fits(int N) { return N <= mw::kSortBoxMax; }
+// Segment length and sort-key bits of k_list_order: the whole box when the full-box kernel stages its positions in LDS (at the
+// ivcap of mw_init), else the 64 molecules of a wavefront; the (key, group) table must fit kOrderSlots.
+void order_plan(int N, int seg_override, int& seg, int& kbits)
+{
+    seg = lds_fits(N, 32) ? ((N + 63) & ~63) : 64;
+    if (seg_override >= 64) seg = (seg_override + 63) & ~63;
+    const size_t seg_groups = ((size_t)std::min(N, seg) + 63) / 64;
+    kbits = -1;
+    for (int kb = 8; kb >= 0; --kb)
+        if ((seg_groups << kb) <= (size_t)mw::kOrderSlots) { kbits = kb; break; }
+}
+size_t order_lds_bytes(int N, int seg, int kbits)
+{
+    return kbits < 0 ? 0 : sizeof(int) * ((((size_t)std::min(N, seg) + 63) / 64) << kbits);
 }
 
 int check_live() { return g.live ? 0 : fail("mw: engine not initialised (call mw_init / energy_init first)"); }
@@ -394,7 +422,7 @@ Geo model_geo(int count)
         int want = (2 * g.cu + count - 1) / count;
         int maxsplit = (g.N + ge.block - 1) / ge.block;
         ge.nsplit = want < 1 ? 1 : (want > maxsplit ? maxsplit : want);
-        ge.shmem = kQueue1024 + mw::lds_vec_bytes((size_t)g.N) + mw::lds_vec_bytes((size_t)g.ivcap);
+        ge.shmem = model_lds_bytes(g.N, g.ivcap);
     } else {
         ge.block = 256;
         ge.nsplit = (g.N + ge.block - 1) / ge.block;
@@ -418,8 +446,7 @@ int launch_model_energy(int first, int count, bool with_mom = false, bool write_
     const int wen = write_energy ? 1 : 0;
     // whole boxes staged in LDS, one workgroup per box: the workgroups are persistent, one per compute unit (its LDS holds
     // one), each taking every g.cu-th box and reading its next box while the current one's tail drains
-    static const bool persist = !(std::getenv("MW_MODEL_PERSIST") && std::getenv("MW_MODEL_PERSIST")[0] == '0');   // 0: one workgroup per box (A/B only)
-    dim3 grid(ge.nsplit, persist && ge.lds && ge.nsplit == 1 ? std::min(count, g.cu) : count);
+    dim3 grid(ge.nsplit, g.model_persist && ge.lds && ge.nsplit == 1 ? std::min(count, g.cu) : count);
     const int box0 = first - 1;
     if (ge.lds && mom)
         hipLaunchKernelGGL((mw::k_model_energy<true, 1024, kFullLayout, false, true>), grid, dim3(1024), ge.shmem, g.stream, g.d_pos, g.d_ivect,
@@ -438,6 +465,11 @@ int launch_model_energy(int first, int count, bool with_mom = false, bool write_
                            g.d_nivect, g.d_list, g.d_order, g.d_nns, g.d_cmax, g.d_partial, g.d_cpartial, g.d_energy, g.d_counts, g.N, g.S, g.ivcap, box0, ge.nsplit, ge.chunk, count,
                            mom, wen);
     HIPCHK(hipGetLastError());
+    {
+        int* d = g.disp[MW_DISPATCH_ENERGY];
+        d[0] = g.ivcap; d[1] = count; d[2] = ge.lds; d[3] = ge.nsplit; d[4] = ge.chunk; d[5] = (int)grid.y; d[6] = mom != nullptr;
+        d[7] = (int)ge.shmem; d[8] = ge.block;
+    }
     if (mom) { g.mom_first = first; g.mom_count = count; g.swm_count = 0; }   // (d_mom rewritten for these boxes: the driver's claim on it ends -- its launch renews it)
     if (ge.nsplit > 1 && write_energy) {           // split boxes: the partials of box b live at [b*nsplit .. b*nsplit+nsplit); unsplit boxes wrote their energy themselves
         hipLaunchKernelGGL(mw::k_sum_partials, dim3(count), dim3(64), 0, g.stream, g.d_partial, g.d_cpartial,
@@ -477,15 +509,17 @@ int launch_model_forces(int first, int count, int timer_slot)
     if (!g.d_mom) return fail("mw_model_forces: no moment buffer");
     if (timed) { HIPCHK(hipEventRecord(g.ev[timer_slot][1], g.stream)); HIPCHK(hipEventRecord(g.ev[timer_slot + 1][0], g.stream)); }
     const int box0 = first - 1;
+    const size_t shmem = lds ? pos_lds_bytes(g.N, g.ivcap) : mw::lds_vec_bytes((size_t)g.ivcap);
     if (lds)
         hipLaunchKernelGGL((mw::k_model_forces<true, kForceBlockLds, kFullLayout>), dim3(1, count), dim3(kForceBlockLds),
-                           mw::lds_vec_bytes((size_t)g.N) + mw::lds_vec_bytes((size_t)g.ivcap), g.stream, g.d_pos, g.d_ivect, g.d_nivect,
+                           shmem, g.stream, g.d_pos, g.d_ivect, g.d_nivect,
                            g.d_list, g.d_order, g.d_nns, g.d_mom, g.d_force, g.d_wpart, g.N, g.S, g.ivcap, box0);
     else
         hipLaunchKernelGGL((mw::k_model_forces<false, kForceBlockGlobal, kFullLayout>), dim3(nsplit, count), dim3(kForceBlockGlobal),
-                           mw::lds_vec_bytes((size_t)g.ivcap), g.stream, g.d_pos, g.d_ivect, g.d_nivect,
+                           shmem, g.stream, g.d_pos, g.d_ivect, g.d_nivect,
                            g.d_list, g.d_order, g.d_nns, g.d_mom, g.d_force, g.d_wpart, g.N, g.S, g.ivcap, box0);
     HIPCHK(hipGetLastError());
+    { int* d = g.disp[MW_DISPATCH_FORCES]; d[0] = g.ivcap; d[1] = count; d[2] = lds; d[3] = nsplit; d[4] = (int)shmem; }
     hipLaunchKernelGGL(mw::k_sum_virial, dim3(count), dim3(64), 0, g.stream, g.d_wpart, g.d_virial, box0, count, nsplit);
     HIPCHK(hipGetLastError());
     if (timed) HIPCHK(hipEventRecord(g.ev[timer_slot + 1][1], g.stream));
@@ -538,15 +572,17 @@ int launch_ice_classes(int first, int count, double rc, int timer_slot)
     }
     const int box0 = first - 1;
     const double rc2 = rc * rc;
+    const size_t shmem = lds ? pos_lds_bytes(g.N, g.ivcap) : mw::lds_vec_bytes((size_t)g.ivcap);
     if (lds)
         hipLaunchKernelGGL((mw::k_ice_q<true, kIceBlockLds, kFullLayout>), dim3(1, count), dim3(kIceBlockLds),
-                           mw::lds_vec_bytes((size_t)g.N) + mw::lds_vec_bytes((size_t)g.ivcap), g.stream, g.d_pos, g.d_ivect, g.d_nivect,
+                           shmem, g.stream, g.d_pos, g.d_ivect, g.d_nivect,
                            g.d_list, g.d_order, g.d_nns, rc2, g.d_iceq, g.d_icenb, g.d_icen, g.d_icecnt, g.N, g.S, g.ivcap, box0);
     else
         hipLaunchKernelGGL((mw::k_ice_q<false, kIceBlockGlobal, kFullLayout>), dim3(nsplit, count), dim3(kIceBlockGlobal),
-                           mw::lds_vec_bytes((size_t)g.ivcap), g.stream, g.d_pos, g.d_ivect, g.d_nivect,
+                           shmem, g.stream, g.d_pos, g.d_ivect, g.d_nivect,
                            g.d_list, g.d_order, g.d_nns, rc2, g.d_iceq, g.d_icenb, g.d_icen, g.d_icecnt, g.N, g.S, g.ivcap, box0);
     HIPCHK(hipGetLastError());
+    { int* d = g.disp[MW_DISPATCH_ICE]; d[0] = g.ivcap; d[1] = count; d[2] = lds; d[3] = nsplit; d[4] = (int)shmem; }
     if (timed) { HIPCHK(hipEventRecord(g.ev[timer_slot][1], g.stream)); HIPCHK(hipEventRecord(g.ev[timer_slot + 1][0], g.stream)); }
     hipLaunchKernelGGL((mw::k_ice_class<kIceBlockClass>), dim3((g.N + kIceBlockClass - 1) / kIceBlockClass, count), dim3(kIceBlockClass), 0,
                        g.stream, g.d_iceq, g.d_icenb, g.d_icen, g.d_icecls, g.d_icecnt, g.N, box0);
@@ -564,8 +600,6 @@ int fetch_ice_classes(int first, int count, uint8_t* cls, int* counts)
     HIPCHK(hipStreamSynchronize(g.stream));
     return 0;
 }
-
-size_t sort_box_lds_bytes() { return (size_t)g.N * 24 + ((size_t)g.cstride + 1) * 4; }
 
 int launch_build(int first, int count)
 {
@@ -586,7 +620,7 @@ int launch_build(int first, int count)
     if (ngrid > 0) {
         if (fused_sort) {
             // boxes whose cell-ordered records fit LDS: bin + scan + scatter in one workgroup per box
-            hipLaunchKernelGGL(mw::k_cell_sort_box, dim3(count), dim3(1024), sort_box_lds_bytes(), g.stream, g.d_pos, g.d_grid,
+            hipLaunchKernelGGL(mw::k_cell_sort_box, dim3(count), dim3(1024), sort_lds_bytes(g.N), g.stream, g.d_pos, g.d_grid,
                                g.d_cstart, g.d_wpos, g.d_wsh, g.d_stats, g.N, g.cstride, box0);
             HIPCHK(hipGetLastError());
         } else {
@@ -637,12 +671,14 @@ int launch_build(int first, int count)
     // the slot-major layout of the full-box kernel, columns sorted by work (mw_neighbours.hip.h, k_list_order)
     {
         const int nseg = (g.N + g.order_seg - 1) / g.order_seg;
-        const int ngroups = (std::min(g.N, g.order_seg) + 63) / 64;
-        const size_t shmem = g.order_kbits < 0 ? 0 : sizeof(int) * ((size_t)ngroups << g.order_kbits);
+        const size_t shmem = order_lds_bytes(g.N, g.order_seg, g.order_kbits);
         const int nthreads = std::min(1024, std::max(64, (std::min(g.N, g.order_seg) + 63) & ~63));
         hipLaunchKernelGGL(mw::k_list_order, dim3(nseg, count), dim3(nthreads), shmem, g.stream, g.d_listm, g.d_nn, g.d_cin, g.d_stats,
                            g.d_list, g.d_order, g.d_nns, g.d_cmax, g.N, g.S, box0, g.order_kbits, g.order_seg);
         HIPCHK(hipGetLastError());
+        int* d = g.disp[MW_DISPATCH_BUILD];
+        d[0] = g.ivcap; d[1] = count; d[2] = ngrid; d[3] = count - ngrid; d[4] = fused_sort; d[5] = ngrid > 0 && g.legacy_search;
+        d[6] = g.order_seg; d[7] = nseg; d[8] = (int)shmem;
     }
     return 0;
 }
@@ -830,14 +866,10 @@ static int init_impl(int device, int nwater, int nboxes, int maxneigh)
         // space: measured on 64 x 32768 molecules, sorting over 256 / 1024 / 32768 molecules costs 16 / 80 / 95 % in
         // cache misses, more than the balance gains).  MW_ORDER_SEG overrides (a multiple of 64).
         // Sort key bits: the (key, group) table must fit kOrderSlots.
-        g.order_seg = lds_fits(nwater, 32) ? ((nwater + 63) & ~63) : 64;
-        if (const char* sg = std::getenv("MW_ORDER_SEG")) { const int v = std::atoi(sg); if (v >= 64) g.order_seg = (v + 63) & ~63; }
-        const size_t seg_groups = ((size_t)std::min(nwater, g.order_seg) + 63) / 64;
-        g.order_kbits = -1;
-        for (int kb = 8; kb >= 0; --kb)
-            if ((seg_groups << kb) <= (size_t)mw::kOrderSlots) { g.order_kbits = kb; break; }
+        const char* sg = std::getenv("MW_ORDER_SEG");
+        order_plan(nwater, sg ? std::atoi(sg) : 0, g.order_seg, g.order_kbits);
     }
-    g.cstride = nwater + 64;
+    g.cstride = cell_stride(nwater);
     HIPCHK(hipMalloc(&g.d_grid, nb * sizeof(mw::GridDesc)));
     HIPCHK(hipMalloc(&g.d_usegrid, nb * sizeof(int)));
     HIPCHK(hipMalloc(&g.d_cellid, nb * N * sizeof(int)));
@@ -849,10 +881,10 @@ static int init_impl(int device, int nwater, int nboxes, int maxneigh)
     { const char* cs = std::getenv("MW_CELL_SEARCH"); g.legacy_search = cs && std::strcmp(cs, "legacy") == 0; }
     {
         const char* cs = std::getenv("MW_CELL_SORT");
-        g.sort_in_lds = nwater <= mw::kSortBoxMax && !(cs && std::strcmp(cs, "global") == 0);
+        g.sort_in_lds = sort_fits(nwater) && !(cs && std::strcmp(cs, "global") == 0);
         if (g.sort_in_lds)
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mw::k_cell_sort_box), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)sort_box_lds_bytes()));
+                                       (int)sort_lds_bytes(nwater)));
     }
     HIPCHK(hipMalloc(&g.d_ccount, nb * (size_t)g.cstride * sizeof(int)));
     HIPCHK(hipMalloc(&g.d_cstart, nb * ((size_t)g.cstride + 1) * sizeof(int)));
@@ -864,6 +896,8 @@ static int init_impl(int device, int nwater, int nboxes, int maxneigh)
     g.h_usegrid.assign(nb, 0);
     g.h_listbuilt.assign(nb, 0);
     { const char* fb = std::getenv("MW_FORCE_BRUTE_NEIGHBOURS"); g.force_brute = fb && *fb && *fb != '0'; }
+    { const char* mm = std::getenv("MW_MOVE_MOMENTS"); g.move_moments = mm ? (mm[0] != '0' ? 1 : 0) : -1; }
+    { const char* mp = std::getenv("MW_MODEL_PERSIST"); g.model_persist = !(mp && mp[0] == '0'); }
     HIPCHK(hipMalloc(&g.d_partial, nb * g.nsplit_max * sizeof(double)));
     HIPCHK(hipMalloc(&g.d_cpartial, nb * g.nsplit_max * 2 * sizeof(unsigned long long)));
     HIPCHK(hipMalloc(&g.d_energy, nb * sizeof(double)));
@@ -1657,34 +1691,39 @@ static int launch_moves(int mode)
     // full-box pass that makes the moments (one pass costs what ~300 requests save; MW_MOVE_MOMENTS=0 | 1 overrides the count rule).
     // The moments must be those of the positions as they are NOW: they are taken from the last full-box launch only when nothing
     // that can move a molecule has run since (mw_step_launch: the full-box pass of the same step), else made here.
-    static const char* momenv = std::getenv("MW_MOVE_MOMENTS");
     const bool mom_ok = g.mlds && g.m_noself && model_geo(1).lds && g.m_boxhi >= g.m_boxlo;
     const bool fresh = g.d_mom && g.mom_count > 0 && g.mom_first - 1 <= g.m_boxlo && g.m_boxhi < g.mom_first - 1 + g.mom_count;
     // (a request saves ~0.3 ns of the launch; a box's moments cost 0.13 us as a by-product of the step's full-box pass, 0.32 us as a
     //  pass of their own: 512 / 1280 requests per box)
-    const bool use_mom = mom_ok && (momenv ? momenv[0] != '0' : g.m_minreq >= (fresh ? 512 : 1280));
+    const bool use_mom = mom_ok && (g.move_moments >= 0 ? g.move_moments != 0 : g.m_minreq >= (fresh ? 512 : 1280));
+    const size_t shmem = g.mlds ? move_lds_bytes(g.N, g.ivcap, g.mchunk) : iv_bytes;
     if (use_mom) {
         if (!fresh && launch_model_energy(g.m_boxlo + 1, g.m_boxhi - g.m_boxlo + 1, true, false)) return 1;
         hipLaunchKernelGGL((mw::k_move_energy<true, mw::kLayoutSoA, false, true>), dim3(g.mwork_n), dim3(1024),
-                           iv_bytes + mw::lds_vec_bytes((size_t)g.N) + (((size_t)g.N + 7) & ~(size_t)7) + (size_t)g.mchunk * sizeof(int), g.stream,
+                           shmem, g.stream,
                            g.d_pos, g.d_ivect, g.d_nivect, g.d_listm, g.d_nn, g.d_mwork, g.d_mimol, g.d_mtrial, g.d_mperm,
                            g.d_meold, g.d_menew, g.d_mcnt, g.d_mdecl, g.N, g.ivcap, kmode, (const double*)g.d_mom, g.d_mtot);
         g.mtot_n = g.mwork_n;
     } else if (g.mlds && g.m_noself)
         hipLaunchKernelGGL((mw::k_move_energy<true, mw::kLayoutSoA, false>), dim3(g.mwork_n), dim3(1024),
-                           iv_bytes + mw::lds_vec_bytes((size_t)g.N) + (((size_t)g.N + 7) & ~(size_t)7) + (size_t)g.mchunk * sizeof(int), g.stream,
+                           shmem, g.stream,
                            g.d_pos, g.d_ivect, g.d_nivect, g.d_listm, g.d_nn, g.d_mwork, g.d_mimol, g.d_mtrial, g.d_mperm,
                            g.d_meold, g.d_menew, g.d_mcnt, g.d_mdecl, g.N, g.ivcap, kmode, (const double*)nullptr, (unsigned int*)nullptr);
     else if (g.mlds)
         hipLaunchKernelGGL(mw::k_move_energy<true>, dim3(g.mwork_n), dim3(1024),
-                           iv_bytes + mw::lds_vec_bytes((size_t)g.N) + (((size_t)g.N + 7) & ~(size_t)7) + (size_t)g.mchunk * sizeof(int), g.stream,
+                           shmem, g.stream,
                            g.d_pos, g.d_ivect, g.d_nivect, g.d_listm, g.d_nn, g.d_mwork, g.d_mimol, g.d_mtrial, g.d_mperm,
                            g.d_meold, g.d_menew, g.d_mcnt, g.d_mdecl, g.N, g.ivcap, kmode, (const double*)nullptr, (unsigned int*)nullptr);
     else
-        hipLaunchKernelGGL(mw::k_move_energy<false>, dim3(g.mwork_n), dim3(1024), iv_bytes, g.stream,
+        hipLaunchKernelGGL(mw::k_move_energy<false>, dim3(g.mwork_n), dim3(1024), shmem, g.stream,
                            g.d_pos, g.d_ivect, g.d_nivect, g.d_listm, g.d_nn, g.d_mwork, g.d_mimol, g.d_mtrial, g.d_mperm,
                            g.d_meold, g.d_menew, g.d_mcnt, g.d_mdecl, g.N, g.ivcap, kmode, (const double*)nullptr, (unsigned int*)nullptr);
     HIPCHK(hipGetLastError());
+    {
+        int* d = g.disp[MW_DISPATCH_MOVES];
+        d[0] = g.ivcap; d[1] = g.mn; d[2] = g.mlds; d[3] = g.m_noself; d[4] = use_mom; d[5] = use_mom && fresh; d[6] = g.mchunk;
+        d[7] = g.mwork_n; d[8] = (int)shmem; d[9] = use_mom ? 3 : (g.mlds ? (g.m_noself ? 2 : 1) : 0);
+    }
     // the requests the fused routine declined (none on ice): plain routine, one wavefront each
     hipLaunchKernelGGL(mw::k_move_fallback, dim3(std::min(1024, (g.mn + 3) / 4)), dim3(256), 0, g.stream, g.d_pos, g.d_ivect, g.d_listm, g.d_nn,
                        g.d_mimol, g.d_mtrial, g.d_mperm, g.d_meold, g.d_menew, g.d_mcnt, g.d_mdecl, g.N, g.ivcap, kmode);
@@ -1712,8 +1751,7 @@ int mw_step_launch(int first_ils, int count, int timer_slot)
         HIPCHK(hipEventRecord(g.ev[timer_slot][0], g.stream));
     }
     // (the step's full-box pass leaves every molecule's moments behind when the step's move kernel will take the moment path)
-    static const char* momenv = std::getenv("MW_MOVE_MOMENTS");
-    const bool want_mom = g.mn > 0 && g.mlds && g.m_noself && (momenv ? momenv[0] != '0' : g.m_minreq >= 512);
+    const bool want_mom = g.mn > 0 && g.mlds && g.m_noself && (g.move_moments >= 0 ? g.move_moments != 0 : g.m_minreq >= 512);
     if (launch_model_energy(first_ils, count, want_mom, true)) return 1;
     if (timed) { HIPCHK(hipEventRecord(g.ev[timer_slot][1], g.stream)); HIPCHK(hipEventRecord(g.ev[timer_slot + 1][0], g.stream)); }
     if (launch_moves(3)) return 1;
@@ -2445,6 +2483,32 @@ int mw_sweep_last_launch(int* nlat, int* ahead, int* residency, int* volume_move
     int* out[6] = {nlat, ahead, residency, volume_moves, lds_bytes, row_stride};
     for (int k = 0; k < 6; ++k) if (out[k]) *out[k] = g.last_sweep[k];
     return 0;
+}
+
+int mw_last_dispatch(int family, int* fields, int nfields)
+{
+    MW_LOCK;
+    if (check_live()) return 1;
+    if (family < 0 || family >= MW_DISPATCH_FAMILIES) return fail("mw_last_dispatch: family %d outside 0..%d", family, MW_DISPATCH_FAMILIES - 1);
+    if (g.disp[family][0] == 0) return fail("mw_last_dispatch: no launch of family %d yet", family);
+    if (fields) for (int k = 0; k < nfields && k < MW_DISPATCH_FIELDS; ++k) fields[k] = g.disp[family][k];
+    return 0;
+}
+
+int mw_lds_plan(int nwater, int image_capacity, int* out, int nout)
+{
+    if (nwater < 1 || nwater > (1 << mw::kJBits) || image_capacity < 1 || image_capacity > MW_MAX_IVECT) return -1;
+    int seg = 0, kbits = 0;
+    order_plan(nwater, 0, seg, kbits);
+    const long long plan[MW_LDS_BUILDS][2] = {
+        {lds_fits(nwater, image_capacity), (long long)model_lds_bytes(nwater, image_capacity)},
+        {lds_fits(nwater, image_capacity), (long long)pos_lds_bytes(nwater, image_capacity)},
+        {lds_fits(nwater, image_capacity), (long long)pos_lds_bytes(nwater, image_capacity)},
+        {lds_fits_move(nwater, image_capacity), (long long)move_lds_bytes(nwater, image_capacity, mw::kMoveChunk)},
+        {sort_fits(nwater), (long long)sort_lds_bytes(nwater)},
+        {seg >= nwater, (long long)order_lds_bytes(nwater, seg, kbits)}};
+    if (out) for (int k = 0; k < 2 * MW_LDS_BUILDS && k < nout; ++k) out[k] = (int)plan[k / 2][k % 2];
+    return MW_LDS_BUILDS;
 }
 
 int mw_sweep_translation(int first_walker, int count, int nmoves, unsigned long long seed, unsigned long long move0, double* log)

@@ -54,7 +54,29 @@ ABI_SYMBOLS = (
     "mw_sweep_get_tables_range", "mw_sweep_set_tables_range",
     "mw_sweep_moves", "mw_sweep_get_volume_moves", "mw_sweep_sync_cells", "mw_sweep_check_flags",
     "mw_sweep_leshift", "mw_sweep_minu", "mw_sweep_swetnam", "mw_sweep_dd", "mw_sweep_windows", "mw_sweep_set_factors", "mw_sweep_get_factors", "mw_sweep_steps", "mw_sweep_get_counters",
+    "mw_last_dispatch", "mw_lds_plan",
 )
+
+#: the kernel families of mw_last_dispatch (MW_DISPATCH_*, by index) and the names of the fields it reports for each
+DISPATCH_FIELDS = {
+    "build": ("ivcap", "boxes", "grid_boxes", "brute_boxes", "fused_sort", "legacy_search", "order_seg", "nseg", "lds_bytes"),
+    "energy": ("ivcap", "boxes", "lds", "nsplit", "chunk", "grid_y", "moments", "lds_bytes", "block"),
+    "moves": ("ivcap", "requests", "mlds", "noself", "use_mom", "fresh", "mchunk", "items", "lds_bytes", "build"),
+    "forces": ("ivcap", "boxes", "lds", "nsplit", "lds_bytes"),
+    "ice": ("ivcap", "boxes", "lds", "nsplit", "lds_bytes"),
+}
+#: the LDS-staged builds of mw_lds_plan (MW_LDS_*, by index)
+LDS_BUILDS = ("energy", "forces", "ice", "move", "sort", "order")
+
+
+def lds_plan(nwater, image_capacity=32):
+    """{build: (admitted, dynamic LDS bytes)} for every LDS-staged build at ``nwater`` molecules and ``image_capacity`` image
+    vectors per box: the engine's own rules (mw_lds_plan), no device needed."""
+    L = load_library()
+    out = (ctypes.c_int * (2 * len(LDS_BUILDS)))()
+    if L.mw_lds_plan(int(nwater), int(image_capacity), out, len(out)) != len(LDS_BUILDS):
+        raise MwError(f"mw_lds_plan: no plan for {nwater} molecules, {image_capacity} image vectors")
+    return {b: (bool(out[2 * k]), int(out[2 * k + 1])) for k, b in enumerate(LDS_BUILDS)}
 
 
 class MwError(RuntimeError):
@@ -495,6 +517,14 @@ class EnergyModule:
         out = np.zeros(8)
         self._chk(self.L.mw_constants(_d(out)))
         return out
+
+    def last_dispatch(self, family):
+        """What the last launch of ``family`` (a key of DISPATCH_FIELDS) did: {field: int} -- which build, its geometry and
+        LDS (include/mw_energy.h, mw_last_dispatch)."""
+        names = DISPATCH_FIELDS[family]
+        out = (ctypes.c_int * len(names))()
+        self._chk(self.L.mw_last_dispatch(list(DISPATCH_FIELDS).index(family), out, len(names)))
+        return dict(zip(names, (int(v) for v in out)))
 
 
 def load_boxes(h_list, xyz_list, maxneigh=MAXNEIGH, device=0):

@@ -86,3 +86,68 @@ def test_eight_small_walkers_share_a_compute_unit(tmp_path):
         assert 0 < dyn and static + dyn <= 20480, (stride, static, dyn)
     assert static + L.mw_sweep_lds_bytes(2, 48, 101, 26, 0, 1, 0) <= 20480          # a sample run carries the unbiased histogram too
     assert L.mw_sweep_lds_bytes(2, 48, 101, 40, 0, 0, 0) == -1 and L.mw_sweep_lds_bytes(2, 100, 101, 20, 0, 0, 0) == -1
+
+
+#: the LDS-staged kernels, by mangled-name prefix, and the build of mw_lds_plan whose dynamic LDS each one asks for
+_LDS_KERNELS = {
+    "_ZN2mw14k_model_energyILb1ELi1024ELi1ELb0ELb0EE": "energy",     # k_model_energy<true, 1024, pair layout>
+    "_ZN2mw14k_model_energyILb1ELi1024ELi1ELb0ELb1EE": "energy",     # ... its MOMOUT build
+    "_ZN2mw13k_move_energyILb1ELi2ELb1ELb0EE": "move",               # k_move_energy<true>: self-images
+    "_ZN2mw13k_move_energyILb1ELi2ELb0ELb0EE": "move",               # ... no self-images
+    "_ZN2mw13k_move_energyILb1ELi2ELb0ELb1EE": "move",               # ... moment path
+    "_ZN2mw14k_model_forcesILb1ELi1024ELi1EE": "forces",
+    "_ZN2mw7k_ice_qILb1ELi1024ELi1EE": "ice",
+    "_ZN2mw15k_cell_sort_box": "sort",
+}
+
+
+def _largest_admitted(build, ivcap):
+    from mc_water_ls_mw_amd.energy import lds_plan
+    lo, hi = 1, 1 << 16
+    assert lds_plan(lo, ivcap)[build][0] and not lds_plan(hi, ivcap)[build][0]
+    while hi - lo > 1:                     # admitted at lo, not at hi
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if lds_plan(mid, ivcap)[build][0] else (lo, mid)
+    return lo
+
+
+def test_lds_thresholds_are_pinned():
+    """Where each LDS-staged build stops being admitted, from the engine's own rules (mw_lds_plan): a change to a budget or to
+    a kernel's LDS layout moves these and has to show up here.  Energy, forces, ice pass 1 and the whole-box list-order segment
+    share one rule; the move kernel stages the requests' molecules too; the fused cell sort has a fixed cap."""
+    from mc_water_ls_mw_amd import build as mwbuild
+    mwbuild.build()
+    want = {32: {"energy": 4490, "forces": 4490, "ice": 4490, "move": 4372, "sort": 5120},
+            48: {"energy": 4474, "forces": 4474, "ice": 4474, "move": 4356, "sort": 5120},
+            64: {"energy": 4458, "forces": 4458, "ice": 4458, "move": 4341, "sort": 5120}}
+    for ivcap, lim in want.items():
+        assert {b: _largest_admitted(b, ivcap) for b in lim} == lim, ivcap
+    assert _largest_admitted("order", 32) == 4490           # (the list order's segment is chosen at mw_init, at 32 image vectors)
+    from mc_water_ls_mw_amd.energy import load_library
+    assert load_library().mw_lds_plan(0, 32, None, 0) == -1 and load_library().mw_lds_plan(100, 0, None, 0) == -1
+
+
+@pytest.mark.skipif(not os.path.exists(READELF), reason="llvm-readelf not in this image")
+def test_static_lds_fits_beside_the_largest_dynamic_request(tmp_path):
+    """The launches may ask for up to 160 KiB - 2 KiB of dynamic LDS (kLdsBudget): the 2 KiB are what each LDS-staged kernel's
+    static __shared__ arrays may take.  Nothing at run time checks that reserve -- a launch at a threshold size would simply
+    fail -- so the code object is held to it: static + dynamic LDS at the largest admitted box <= 160 KiB, for 32, 48 and 64
+    image vectors per box."""
+    from mc_water_ls_mw_amd import build as mwbuild
+    from mc_water_ls_mw_amd.energy import lds_plan
+    mwbuild.build()
+    notes = subprocess.run([READELF, "--notes", _gfx950_code_object(tmp_path)], capture_output=True, text=True, check=True).stdout
+    static = {}
+    for blk in notes.split("- .agpr_count")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
+        for prefix in _LDS_KERNELS:
+            if name.startswith(prefix):
+                assert prefix not in static, name
+                static[prefix] = int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", blk).group(1))
+    assert sorted(static) == sorted(_LDS_KERNELS)
+    for ivcap in (32, 48, 64):
+        for prefix, build in _LDS_KERNELS.items():
+            n = _largest_admitted(build, ivcap)
+            dyn = lds_plan(n, ivcap)[build][1]
+            assert static[prefix] + dyn <= 160 * 1024, (prefix, ivcap, n, static[prefix], dyn)
+            assert static[prefix] <= 2048, (prefix, static[prefix])

@@ -71,9 +71,10 @@ def test_4096_boxes_match_reference(name, c_oracle):
     _check_case(load_golden(name), c_oracle, full_lists=False)
 
 
-def test_32768_stress_box_list_rebuild_and_full_energy():
+def test_32768_stress_box_list_rebuild_and_full_energy(c_oracle):
     """BASELINE.json configs[4]: 32768-molecule ice Ih, neighbour-list rebuild + full energy
-    (positions do not fit LDS: the full-box kernel gathers from L2)."""
+    (positions do not fit LDS: the full-box kernel gathers from L2), every local energy, trial moves."""
+    from mc_water_ls_mw_amd import lattice as lat
     z = load_golden("ih32768_t015")
     em = _engine(z)
     try:
@@ -82,11 +83,24 @@ def test_32768_stress_box_list_rebuild_and_full_energy():
         assert list_digest(nn, jn, vn) == str(z["list_sha256"])
         e_ref = float(z["model_energy"])
         assert abs(em.model_energy[0] - e_ref) <= RTOL * abs(e_ref)
+        assert em.last_dispatch("energy")["lds"] == 0
         loc = em.local_energy_batch(1, np.arange(1, int(z["n"]) + 1))
         assert abs(loc.sum() - float(z["local_sum"])) <= RTOL * abs(float(z["local_sum"]))
         # G4: sum_i local = 2 E2 + 3 E3 and model = E2 + E3, so E3 = sum_local - 2 model must be positive and small
         e3 = loc.sum() - 2 * em.model_energy[0]
         assert 0 < e3 < 0.2 * abs(e_ref)
+        # every molecule, and seeded trial moves through the L2-gather move kernel, against the oracle on the engine's own
+        # list (entry for entry the reference's, by the digest above: no O(N^2) oracle build at this size)
+        iv = em.ivect(1)
+        ref = c_oracle.local_energy_all(z["xyz"], iv, nn, jn, vn)
+        assert np.all(np.abs(loc - ref) <= RTOL * np.abs(ref)), np.abs(loc - ref).max()
+        imol, trial = lat.trial_moves(z["xyz"], 3000, seed=32768)
+        for k in (3000, 7):                                               # many requests per work item, then a handful
+            eo, en = em.delta_energy_batch(1, imol[:k], trial[:k])
+            assert em.last_dispatch("moves")["build"] == 0                # (k_move_energy<false>: the box does not fit LDS)
+            ro, rn = c_oracle.trial_moves(imol[:k], trial[:k], z["xyz"], iv, nn, jn, vn)
+            assert np.all(np.abs(eo - ro) <= RTOL * np.abs(ro)) and np.all(np.abs(en - rn) <= RTOL * np.abs(rn))
+            assert np.all(np.abs((en - eo) - (rn - ro)) <= DE_ATOL)
     finally:
         em.energy_deinit()
 
@@ -489,6 +503,8 @@ def test_moment_path_of_the_move_kernel_and_the_triplets_it_must_decline(moments
         trial = x[imol - 1] + rng.normal(0.0, 0.4, (len(imol), 3))
         trial[:3] = x[imol[:3] - 1]                                       # (unmoved: old == new, the dropped terms on both sides)
         eo, en = em.delta_energy_batch(1, imol, trial)
+        d = em.last_dispatch("moves")                                     # the path the case names, on the same requests
+        assert d["mlds"] == 1 and d["noself"] == 1 and d["use_mom"] == (moments == "1") and d["build"] == (3 if moments == "1" else 2)
         ro, rn = c_oracle.trial_moves(imol, trial, x, iv, nn, jn, vn)
         assert np.all(np.abs(eo - ro) <= RTOL * np.abs(ro)) and np.all(np.abs((en - eo) - (rn - ro)) <= DE_ATOL)
         # the pushed molecule really does make such triplets: with the 0.99 rule ignored, b's local energy would be off by far more than the tolerance
