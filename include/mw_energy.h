@@ -41,7 +41,8 @@ extern "C" {
 #define MW_DISPATCH_MOVES    2
 #define MW_DISPATCH_FORCES   3
 #define MW_DISPATCH_ICE      4
-#define MW_DISPATCH_FAMILIES 5
+#define MW_DISPATCH_RDF      5
+#define MW_DISPATCH_FAMILIES 6
 #define MW_DISPATCH_FIELDS   10
 
 /* LDS-staged builds of mw_lds_plan */
@@ -159,6 +160,24 @@ int mw_ice_classes_launch(int first_ils, int count, double rc, int timer_slot);
  * fastest): c = q_i.q_j / (|q_i| |q_j|) for a neighbour entry, NaN where q_i or q_j is degenerate, 1 for an image of i
  * itself, exactly 2.0 for an entry that is not a bond (unused slot, |d| >= rc or |d| = 0). */
 int mw_ice_bonds(int ils, double rc, double *c);
+
+/* ---- pair-distance histogram for g(r) and n(r) (no counterpart in the reference) ----------------------------------- */
+
+/* hist[b], b = 0 .. nbins-1: the number of ordered triples (i, j, n) -- n any integer lattice translation, (j, n) != (i, 0) --
+ * with d = |r_j + n1 h1 + n2 h2 + n3 h3 - r_i|, 0 < d < r_max (bohr) and b = floor(d nbins / r_max), of box ils: the
+ * pair-distance histogram of the periodic system (images of i itself count), from the mirrored positions, wrapped or not,
+ * and the cell the DEVICE holds (after sweeps with volume moves that is the current one); all pairs, no neighbour list.
+ * 1 <= nbins <= 4096 and 0 < r_max, r_max (1 + 1e-9) <= 1.5 x the smallest perpendicular width of the cell (three images per
+ * axis cover no more): anything else fails with a message that names r_max or nbins and writes nothing.  Counts are exact
+ * integers and do not depend on which other boxes share a launch.  Positions, cells, lists, energies and moments are not
+ * touched.  g(r) and n(r) are host arithmetic on hist (energy.rdf_from_counts). */
+int mw_rdf(int ils, double r_max, int nbins, long long *hist);
+/* The same for boxes first_ils .. first_ils+count-1 in one launch: hist = count x nbins.  Every box of the call must admit
+ * r_max; the message names the first one that does not. */
+int mw_rdf_batch(int first_ils, int count, double r_max, int nbins, long long *hist);
+/* The launch of mw_rdf_batch without the copy-back (results stay on the device; mw_sync waits for them).
+ * timer_slot >= 0: event timer timer_slot around it. */
+int mw_rdf_launch(int first_ils, int count, double r_max, int nbins, int timer_slot);
 
 /* ---- compute_local_real_energy(imol, ils) (molint.F90:220-404) ------------------- */
 
@@ -334,6 +353,8 @@ int mw_sweep_lds_bytes(int nlat, int nwater, int nbins, int row_stride, int volu
  *            full-box pass (fresh), requests per work item (mchunk), work items, dynamic LDS, build (0 L2 gather, 1 LDS with
  *            self-images, 2 LDS without, 3 moment path)
  *   FORCES, ICE : ivcap, boxes, box staged in LDS, workgroups per box, dynamic LDS
+ *   RDF    : ivcap, boxes, small-box geometry (one wavefront per box), workgroups per box, dynamic + static LDS, images per
+ *            pair (1, 3, 9 or 27: the largest of the launch's boxes)
  * The full-box family also reports the moment passes that the move, force and driver launches run for themselves. */
 int mw_last_dispatch(int family, int *fields, int nfields);
 /* For `nwater` molecules and `image_capacity` image vectors per box, out[2 k] = whether LDS build k (MW_LDS_*) is admitted and

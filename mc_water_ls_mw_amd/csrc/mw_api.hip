@@ -77,6 +77,9 @@ struct Ctx {
     int* d_icecnt = nullptr;           // [box][kIceClasses]: its class counts
     double* d_icebond = nullptr;       // [N][S]: the bond values of mw_ice_bonds' box
     bool ice_attr = false;             // the LDS-staged pass 1's dynamic LDS limit has been raised
+    unsigned long long* d_rdf = nullptr;   // [box][nbins of the last call]: pair-distance histograms of the last mw_rdf* call
+    size_t rdf_bins = 0;               // ... allocated for nbox x rdf_bins counts (grown on demand)
+    bool rdf_attr = false;             // k_rdf_small's dynamic LDS limit has been raised
     double* d_mom = nullptr;           // [box][N][kMomStride]: per-molecule moments (k_model_energy's by-product) for the single-move kernel's moment path
     int mom_first = 0, mom_count = 0;  // the boxes whose moments the LAST full-box launch left valid (cleared by everything that may move a molecule)
     int swm_first = 0, swm_count = 0;  // the boxes (1-based first) whose moments in d_mom the Monte Carlo driver keeps current from launch to launch
@@ -601,6 +604,85 @@ int fetch_ice_classes(int first, int count, uint8_t* cls, int* counts)
     return 0;
 }
 
+// Pair-distance histograms (mw_rdf.hip.h).  The cells are the DEVICE's (d_hmat: authoritative after volume moves), read back
+// here for the one check that needs them: r_max (1 + 1e-9) <= 1.5 x the smallest perpendicular width of every box of the call,
+// beyond which three images per axis no longer cover r_max.  Nothing is launched or written unless every box passes.
+// Boxes of N <= kRdfSmallMax: one wavefront per box (k_rdf_small); larger: ceil(N / kRdfTile) workgroups per box (k_rdf_tiles).
+int check_rdf_args(const char* who, double r_max, int nbins)
+{
+    if (!(r_max > 0.0) || !(r_max < 1e300)) return fail("%s: r_max = %g bohr outside (0, 1.5 x the smallest cell width]", who, r_max);
+    if (nbins < 1 || nbins > mw::kRdfMaxBins) return fail("%s: nbins = %d outside 1..%d", who, nbins, mw::kRdfMaxBins);
+    return 0;
+}
+
+int launch_rdf(const char* who, int first, int count, double r_max, int nbins, int timer_slot)
+{
+    const int box0 = first - 1;
+    std::vector<double> h((size_t)count * 9);
+    HIPCHK(hipMemcpyAsync(h.data(), g.d_hmat + 9 * (size_t)box0, h.size() * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    int images = 1;
+    for (int b = 0; b < count; ++b) {
+        double w[3];
+        mw::rdf_cell_widths(&h[(size_t)b * 9], nullptr, w);
+        int n = 1;
+        for (int k = 0; k < 3; ++k) {
+            const int m = mw::rdf_axis_images(r_max, w[k]);
+            if (m < 0)
+                return fail("%s: r_max = %.17g bohr outside (0, %.17g] = 1.5 x the smallest cell width of box %d (widths %g %g %g bohr)",
+                            who, r_max, 1.5 * std::min(w[0], std::min(w[1], w[2])) / (1.0 + 1e-9), first + b, w[0], w[1], w[2]);
+            n *= 2 * m + 1;
+        }
+        images = std::max(images, n);
+    }
+    if (!g.d_rdf || g.rdf_bins < (size_t)nbins) {
+        if (g.d_rdf) { HIPCHK(hipFree(g.d_rdf)); g.d_rdf = nullptr; g.rdf_bins = 0; }
+        HIPCHK(hipMalloc(&g.d_rdf, (size_t)g.nbox * nbins * sizeof(unsigned long long)));
+        g.rdf_bins = (size_t)nbins;
+    }
+    const bool timed = timer_slot >= 0;
+    if (timed) {
+        if (timer_slot >= kTimerSlots) return fail("%s: timer slot %d outside 0..%d", who, timer_slot, kTimerSlots - 1);
+        if (!g.ev[timer_slot][0]) { HIPCHK(hipEventCreate(&g.ev[timer_slot][0])); HIPCHK(hipEventCreate(&g.ev[timer_slot][1])); }
+        HIPCHK(hipEventRecord(g.ev[timer_slot][0], g.stream));
+    }
+    unsigned long long* out = g.d_rdf + (size_t)box0 * nbins;
+    const bool small = g.N <= mw::kRdfSmallMax;
+    int per_box = 1;
+    size_t lds = 0;
+    if (small) {
+        lds = (size_t)mw::kRdfSmallWaves * (3 * mw::kRdfSmallMax * sizeof(double) + (size_t)nbins * sizeof(unsigned));
+        if (!g.rdf_attr) {
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mw::k_rdf_small), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)(mw::kRdfSmallWaves * (3 * mw::kRdfSmallMax * sizeof(double) + mw::kRdfMaxBins * sizeof(unsigned)))));
+            g.rdf_attr = true;
+        }
+        hipLaunchKernelGGL(mw::k_rdf_small, dim3((count + mw::kRdfSmallWaves - 1) / mw::kRdfSmallWaves), dim3(64 * mw::kRdfSmallWaves),
+                           lds, g.stream, g.d_pos, g.d_hmat, r_max, nbins, out, g.N, count, box0);
+    } else {
+        per_box = (g.N + mw::kRdfTile - 1) / mw::kRdfTile;
+        if ((unsigned long long)per_box * (unsigned long long)count > 0x7fffffffull)
+            return fail("%s: %d boxes x %d workgroups exceed one launch", who, count, per_box);
+        HIPCHK(hipMemsetAsync(out, 0, (size_t)count * nbins * sizeof(unsigned long long), g.stream));
+        const size_t dyn = (size_t)nbins * sizeof(unsigned);
+        lds = dyn + 3 * mw::kRdfTile * sizeof(double);
+        hipLaunchKernelGGL(mw::k_rdf_tiles, dim3((unsigned)per_box * (unsigned)count), dim3(mw::kRdfTile), dyn, g.stream,
+                           g.d_pos, g.d_hmat, r_max, nbins, out, g.N, per_box, box0);
+    }
+    HIPCHK(hipGetLastError());
+    { int* d = g.disp[MW_DISPATCH_RDF]; d[0] = g.ivcap; d[1] = count; d[2] = small; d[3] = per_box; d[4] = (int)lds; d[5] = images; }
+    if (timed) HIPCHK(hipEventRecord(g.ev[timer_slot][1], g.stream));
+    return 0;
+}
+
+int fetch_rdf(int first, int count, int nbins, long long* hist)
+{
+    HIPCHK(hipMemcpyAsync(hist, g.d_rdf + (size_t)(first - 1) * nbins, (size_t)count * nbins * sizeof(long long),
+                          hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    return 0;
+}
+
 int launch_build(int first, int count)
 {
     const int box0 = first - 1;
@@ -717,7 +799,7 @@ void release_all()
                     g.d_usegrid, g.d_cellid, g.d_shift, g.d_sorted, g.d_wrel, g.d_wpos, g.d_wsh, g.d_ccount, g.d_cstart, g.d_ccursor, g.d_partial,
                     g.d_cpartial, g.d_energy, g.d_counts, g.d_mimol, g.d_mtrial, g.d_meold, g.d_menew, g.d_mcnt, g.d_mperm, g.d_mdecl,
                     g.d_mwork, g.d_mom, g.d_mtot, g.d_wmom, g.d_pm, g.d_srvmomok, g.d_force, g.d_wpart, g.d_virial,
-                    g.d_iceq, g.d_icenb, g.d_icen, g.d_icecls, g.d_icecnt, g.d_icebond};
+                    g.d_iceq, g.d_icenb, g.d_icen, g.d_icecls, g.d_icecnt, g.d_icebond, g.d_rdf};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (g.ev_srv) { (void)hipEventDestroy(g.ev_srv); g.ev_srv = nullptr; }
     if (g.h_pin) (void)hipHostFree(g.h_pin);
@@ -1319,6 +1401,31 @@ int mw_ice_bonds(int ils, double rc, double* c)
     HIPCHK(hipMemcpyAsync(c, g.d_icebond, n * sizeof(double), hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
     return 0;
+}
+
+int mw_rdf_launch(int first_ils, int count, double r_max, int nbins, int timer_slot)
+{
+    MW_LOCK;
+    if (check_live() || check_range(first_ils, count) || check_rdf_args("mw_rdf_launch", r_max, nbins)) return 1;
+    return launch_rdf("mw_rdf_launch", first_ils, count, r_max, nbins, timer_slot);
+}
+
+int mw_rdf_batch(int first_ils, int count, double r_max, int nbins, long long* hist)
+{
+    MW_LOCK;
+    if (check_live() || check_range(first_ils, count) || check_rdf_args("mw_rdf_batch", r_max, nbins)) return 1;
+    if (!hist) return fail("mw_rdf_batch: null pointer");
+    if (launch_rdf("mw_rdf_batch", first_ils, count, r_max, nbins, -1)) return 1;
+    return fetch_rdf(first_ils, count, nbins, hist);
+}
+
+int mw_rdf(int ils, double r_max, int nbins, long long* hist)
+{
+    MW_LOCK;
+    if (check_live() || check_box(ils) || check_rdf_args("mw_rdf", r_max, nbins)) return 1;
+    if (!hist) return fail("mw_rdf: null pointer");
+    if (launch_rdf("mw_rdf", ils, 1, r_max, nbins, -1)) return 1;
+    return fetch_rdf(ils, 1, nbins, hist);
 }
 
 int mw_model_energy_counts(int ils, long long* npairs, long long* ntriplets)

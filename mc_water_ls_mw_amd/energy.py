@@ -42,6 +42,7 @@ ABI_SYMBOLS = (
     "mw_model_energy_counts_total", "mw_neighbour_total",
     "mw_model_forces", "mw_model_forces_batch", "mw_model_forces_launch",
     "mw_ice_classes", "mw_ice_classes_batch", "mw_ice_classes_launch", "mw_ice_bonds",
+    "mw_rdf", "mw_rdf_batch", "mw_rdf_launch",
     "mw_local_energy", "mw_local_energy_patched", "mw_local_energy_post", "mw_local_energy_collect",
     "mw_local_energy_batch", "mw_delta_energy_batch",
     "mw_moves_upload", "mw_moves_launch", "mw_moves_fetch", "mw_moves_counts",
@@ -64,6 +65,7 @@ DISPATCH_FIELDS = {
     "moves": ("ivcap", "requests", "mlds", "noself", "use_mom", "fresh", "mchunk", "items", "lds_bytes", "build"),
     "forces": ("ivcap", "boxes", "lds", "nsplit", "lds_bytes"),
     "ice": ("ivcap", "boxes", "lds", "nsplit", "lds_bytes"),
+    "rdf": ("ivcap", "boxes", "small", "workgroups_per_box", "lds_bytes", "images"),
 }
 #: the LDS-staged builds of mw_lds_plan (MW_LDS_*, by index)
 LDS_BUILDS = ("energy", "forces", "ice", "move", "sort", "order")
@@ -147,6 +149,23 @@ ICE_RC_ANG = 3.5
 
 def _rc(rc_ang):
     return ctypes.c_double(float(rc_ang) / 0.5291772108)          # Angstrom -> bohr (constants.f90:42-43)
+
+
+def rdf_from_counts(hist, nwater, volume_bohr3, r_max_ang):
+    """(r_ang [nbins], g [..., nbins], n [..., nbins]) from pair-distance histograms ``hist`` [..., nbins] (mw_rdf: ordered
+    pairs, periodic images included) of boxes of ``nwater`` molecules and volume ``volume_bohr3`` (a scalar or one per
+    leading index): g[b] = hist[b] / (N (N / V) 4 pi / 3 ((b+1)^3 - b^3) dr^3), the bin centres r[b] = (b + 1/2) dr, and
+    n[b] = cumsum(hist)[b] / N, the neighbours within the bin's upper edge.  Host arithmetic only."""
+    hist = np.asarray(hist)
+    nbins = hist.shape[-1]
+    dr_ang = float(r_max_ang) / nbins
+    dr = dr_ang / 0.5291772108                                     # Angstrom -> bohr (constants.f90:42-43)
+    b = np.arange(nbins, dtype=np.float64)
+    shell = 4.0 * np.pi / 3.0 * ((b + 1.0) ** 3 - b ** 3) * dr ** 3
+    n = float(nwater)
+    vol = np.asarray(volume_bohr3, dtype=np.float64)[..., None]
+    g = hist / (n * (n / vol) * shell)
+    return (b + 0.5) * dr_ang, g, np.cumsum(hist, axis=-1) / n
 
 
 class EnergyModule:
@@ -360,6 +379,31 @@ class EnergyModule:
         c = np.zeros((self.nwater, self.maxneigh))
         self._chk(self.L.mw_ice_bonds(ils, _rc(rc_ang), _d(c)))
         return c
+
+    # -- pair-distance histogram, g(r) and n(r) (no counterpart in the reference) --------
+    def rdf_counts(self, ils, r_max_ang, nbins):
+        """int64 [nbins]: the pair-distance histogram of lattice ils (mw_rdf: ordered pairs with all periodic images inside
+        ``r_max_ang``, Angstrom) from the positions and the cell the DEVICE holds."""
+        self._ils(ils)
+        hist = np.zeros(max(int(nbins), 0), dtype=np.int64)
+        self._chk(self.L.mw_rdf(ils, _rc(r_max_ang), int(nbins), hist.ctypes.data_as(_llp)))
+        return hist
+
+    def rdf_counts_batch(self, first_ils=1, count=None, r_max_ang=10.0, nbins=200):
+        """int64 [count, nbins]: the pair-distance histograms of ``count`` boxes in one launch."""
+        count = self.num_lattices - first_ils + 1 if count is None else count
+        self._ils(first_ils), self._ils(first_ils + count - 1)
+        hist = np.zeros((count, max(int(nbins), 0)), dtype=np.int64)
+        self._chk(self.L.mw_rdf_batch(first_ils, count, _rc(r_max_ang), int(nbins), hist.ctypes.data_as(_llp)))
+        return hist
+
+    def rdf_launch(self, first_ils, count, r_max_ang, nbins, timer_slot=-1):
+        """The launch of rdf_counts_batch, results left on the device; timer_slot >= 0: an event timer around it."""
+        self._chk(self.L.mw_rdf_launch(first_ils, count, _rc(r_max_ang), int(nbins), timer_slot))
+
+    def rdf(self, ils, r_max_ang=10.0, nbins=200):
+        """(r_ang, g, n) of lattice ils: rdf_from_counts of rdf_counts with this module's volume[ils - 1]."""
+        return rdf_from_counts(self.rdf_counts(ils, r_max_ang, nbins), self.nwater, self.volume[ils - 1], r_max_ang)
 
     def model_energy_counts(self, ils):
         p, t = ctypes.c_longlong(0), ctypes.c_longlong(0)

@@ -46,6 +46,7 @@ module energy
   public :: energy_fetch_neighbours   ! extension: fill nn/jn/vn from the device list
   public :: compute_model_forces      ! extension: forces and virial of the full-box energy
   public :: compute_ice_classes       ! extension: CHILL+ ice structure class of every molecule
+  public :: compute_rdf               ! extension: pair-distance histogram of a lattice, for g(r) and n(r)
 
   ! current energy due to the model Hamiltonian (host array, written by callers too)
   real(kind=dp),allocatable,dimension(:),save :: model_energy
@@ -152,6 +153,12 @@ module energy
        integer(c_int8_t),intent(out) :: cls(*)
        integer(c_int),intent(out) :: counts(6)
      end function mw_ice_classes
+     integer(c_int) function mw_rdf(ils,r_max,nbins,hist) bind(C,name="mw_rdf")
+       import :: c_int,c_double,c_long_long
+       integer(c_int),value :: ils,nbins
+       real(c_double),value :: r_max
+       integer(c_long_long),intent(out) :: hist(*)
+     end function mw_rdf
      integer(c_int) function mw_local_energy_patched(ils,imol,r_imol,imol_prev,r_prev,e) &
           bind(C,name="mw_local_energy_patched")
        import :: c_int,c_double
@@ -452,6 +459,27 @@ contains
     call mw_check(mw_ice_classes(int(ils,c_int),real(rc,c_double),cls,counts),'compute_ice_classes')
     return
   end subroutine compute_ice_classes
+
+  subroutine compute_rdf(ils,r_max,nbins,hist)
+    !------------------------------------------------------------------------------!
+    ! Extension: pair-distance histogram of lattice ils from the host's ljr,        !
+    ! mirrored first, and the cell of the last compute_ivects.  hist(b+1) = ordered !
+    ! pairs (i,j) and periodic images with b <= d nbins / r_max < b+1, d < r_max    !
+    ! (bohr), r_max <= 1.5 x the smallest cell width, nbins <= 4096.  Then          !
+    ! g(b) = hist(b+1) / (N (N/V) 4 pi/3 ((b+1)^3 - b^3) (r_max/nbins)^3) and       !
+    ! n(b) = sum(hist(1:b+1)) / N.                                                   !
+    !------------------------------------------------------------------------------!
+    use model, only : ljr
+    implicit none
+    integer,intent(in) :: ils,nbins
+    real(kind=dp),intent(in) :: r_max
+    integer(c_long_long),intent(out) :: hist(nbins)
+    call mw_check(mw_upload_positions(int(ils,c_int),ljr(:,1,:,ils)),'compute_rdf')
+    last_imol(ils) = 0
+    stale(ils) = .false.
+    call mw_check(mw_rdf(int(ils,c_int),real(r_max,c_double),int(nbins,c_int),hist),'compute_rdf')
+    return
+  end subroutine compute_rdf
 
   subroutine compute_neighbours(ils)
     !------------------------------------------------------------------------------!

@@ -300,6 +300,18 @@ class WalkerFarm:
         _, counts = self.em.ice_classes_batch(1, self.em.num_lattices, rc_ang)
         return counts.reshape(self.nwalkers, self.nlat, 6) / float(self.em.nwater)
 
+    def rdf(self, r_max_ang=10.0, nbins=200):
+        """(r_ang [nbins], g [nlat, nbins], n [nlat, nbins]): the radial distribution function and the running coordination
+        number of every lattice, averaged over the walkers, from the positions and cells the device holds (the cells read
+        back through :meth:`sync_cells` first).  One batch of pair-distance histograms over all boxes, each box normalised
+        with its own volume; ``r_max_ang`` may reach 1.5 x the smallest cell width of any box."""
+        from .energy import rdf_from_counts
+        self.sync_cells()
+        hist = self.em.rdf_counts_batch(1, self.em.num_lattices, r_max_ang, nbins)
+        r, g, n = rdf_from_counts(hist, self.em.nwater, self.em.volume, r_max_ang)
+        shape = (self.nwalkers, self.nlat, int(nbins))
+        return r, g.reshape(shape).mean(axis=0), n.reshape(shape).mean(axis=0)
+
     # -- chain synchronisation (mc_check_chain_synchronisation, mc_moves.F90:2217-2416) -------------------------
     def set_reference(self):
         """Remember the reference configuration (ref_hmatrix / ref_ljr of init.f90:90,106) from the host's current
