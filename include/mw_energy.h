@@ -161,6 +161,35 @@ int mw_ice_classes_launch(int first_ils, int count, double rc, int timer_slot);
  * itself, exactly 2.0 for an entry that is not a bond (unused slot, |d| >= rc or |d| = 0). */
 int mw_ice_bonds(int ils, double rc, double *c);
 
+/* ---- ice clusters: connected clusters of molecules of selected CHILL+ classes (no counterpart in the reference) ------ */
+
+/* Clusters of box ils from a classification with bond cutoff rc (the rules of mw_ice_classes, run by this call) and a class
+ * mask: bit k selects class k, 1 <= k <= 5 (1 cubic, 2 hexagonal, 3 interfacial ice, 4 clathrate, 5 interfacial clathrate).
+ * mask must be non-zero and a subset of 0x3e; bit 0 ("other") is refused: such molecules need not have four neighbours, so
+ * their bonds are not kept.  Molecule i is selected iff bit cls[i] of mask is set.  Selected i and selected j are bonded iff
+ * j is one of i's four CHILL+ neighbour entries or i is one of j's (undirected by construction); an entry that is an image
+ * of i itself is no bond, several images of one j are one bond.  Clusters are the connected components through the periodic
+ * boundary.  label = nwater int32 in molecule order: 0 for a molecule that is not selected, else the 1-based index of the
+ * smallest molecule of its cluster (a canonical form: results compare with ==).  summary = {selected molecules, clusters,
+ * size of the largest cluster, label of the largest cluster}, a tie going to the smallest label, all 0 when nothing is
+ * selected.  Either pointer may be NULL.  Nothing else is written: positions, lists, energies and moments are untouched and
+ * the class results the engine holds are those of mw_ice_classes(ils, rc, ..).  Whether a cluster spans the cell is not
+ * reported (DESIGN.md "Ice clusters"). */
+int mw_ice_clusters(int ils, double rc, int mask, int *label, int summary[4]);
+/* The same for boxes first_ils .. first_ils+count-1, one launch per pass: label = count x nwater, summary = count x 4. */
+int mw_ice_clusters_batch(int first_ils, int count, double rc, int mask, int *label, int *summary);
+/* The launches of mw_ice_clusters_batch without the copy-back (results stay on the device; mw_sync waits for them).
+ * timer_slot >= 0: event timers timer_slot and timer_slot + 1 around the two classification passes, timer_slot + 2 around
+ * the cluster pass. */
+int mw_ice_clusters_launch(int first_ils, int count, double rc, int mask, int timer_slot);
+/* Host arithmetic only (no device, no mw_init): out = {labels and sizes of a box of nwater molecules fit LDS, threads per
+ * workgroup, dynamic LDS bytes (0 for the global variant), the largest nwater the LDS variant admits}.  One workgroup per
+ * box either way; MW_ICE_CLUSTERS_LDS=0 at mw_init forces the global variant at any size. */
+int mw_ice_clusters_plan(int nwater, int out[4]);
+/* What the last cluster launch did: out = {boxes, LDS variant used, threads per workgroup, the largest number of
+ * hook / compress rounds any of its boxes took}; all 0 before the first launch.  Waits for the launch. */
+int mw_ice_clusters_last(int out[4]);
+
 /* ---- pair-distance histogram for g(r) and n(r) (no counterpart in the reference) ----------------------------------- */
 
 /* hist[b], b = 0 .. nbins-1: the number of ordered triples (i, j, n) -- n any integer lattice translation, (j, n) != (i, 0) --

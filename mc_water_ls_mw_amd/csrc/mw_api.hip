@@ -77,6 +77,12 @@ struct Ctx {
     int* d_icecnt = nullptr;           // [box][kIceClasses]: its class counts
     double* d_icebond = nullptr;       // [N][S]: the bond values of mw_ice_bonds' box
     bool ice_attr = false;             // the LDS-staged pass 1's dynamic LDS limit has been raised
+    int* d_icelabel = nullptr;         // [box][N]: cluster labels of the last mw_ice_clusters* call (allocated on first use)
+    int* d_icesize = nullptr;          // [box][N]: the global variant's per-root sizes (allocated when that variant first runs)
+    int* d_icesum = nullptr;           // [box][4] summaries, then [box] hook / compress rounds
+    bool clusters_attr = false;        // the LDS variant's dynamic LDS limit has been raised
+    bool clusters_lds = true;          // MW_ICE_CLUSTERS_LDS at mw_init (0: the global variant at any size)
+    int clast[4] = {0, 0, 0, 0};       // the last cluster launch: first box (1-based), boxes, LDS variant, threads per workgroup
     unsigned long long* d_rdf = nullptr;   // [box][nbins of the last call]: pair-distance histograms of the last mw_rdf* call
     size_t rdf_bins = 0;               // ... allocated for nbox x rdf_bins counts (grown on demand)
     bool rdf_attr = false;             // k_rdf_small's dynamic LDS limit has been raised
@@ -604,6 +610,66 @@ int fetch_ice_classes(int first, int count, uint8_t* cls, int* counts)
     return 0;
 }
 
+// Clusters of the molecules of the classes in `mask` (mw_ice_clusters.hip.h): the two classification passes above, then
+// k_ice_clusters over their classes and neighbour entries, one workgroup per box.  Labels and sizes in LDS (8 B per molecule)
+// where that fits 160 KiB less the kernel's static LDS, else in global memory; MW_ICE_CLUSTERS_LDS=0 forces the latter.
+// timer_slot >= 0: event timers timer_slot and timer_slot + 1 (the classification passes) and timer_slot + 2 (the cluster pass).
+constexpr int kClusterLdsBudget = 160 * 1024 - mw::kClusterStaticLds;
+size_t cluster_lds_bytes(int N) { return ((size_t)N * 2 * sizeof(int) + 15) & ~(size_t)15; }
+bool cluster_lds_fits(int N) { return cluster_lds_bytes(N) <= (size_t)kClusterLdsBudget; }
+int cluster_threads(int N) { return std::min(mw::kClusterMaxBlock, std::max(64, (N + 63) & ~63)); }
+int check_cluster_mask(const char* who, int mask)
+{
+    if (mask & 1) return fail("%s: mask %d selects class 0 (other): such molecules need not have four neighbours, their bonds are not kept", who, mask);
+    if (mask <= 0 || (mask & ~mw::kClusterMaskAll)) return fail("%s: mask %d is not a non-empty subset of classes 1..5 (0x%x)", who, mask, mw::kClusterMaskAll);
+    return 0;
+}
+
+int launch_ice_clusters(const char* who, int first, int count, double rc, int mask, int timer_slot)
+{
+    const bool timed = timer_slot >= 0;
+    if (timed && timer_slot + 2 >= kTimerSlots) return fail("%s: timer slot %d outside 0..%d", who, timer_slot, kTimerSlots - 3);
+    const bool lds = g.clusters_lds && cluster_lds_fits(g.N);
+    const size_t nm = (size_t)g.nbox * g.N;
+    if (!g.d_icelabel) {
+        HIPCHK(hipMalloc(&g.d_icelabel, nm * sizeof(int)));
+        HIPCHK(hipMalloc(&g.d_icesum, (size_t)g.nbox * 5 * sizeof(int)));
+    }
+    if (!lds && !g.d_icesize) HIPCHK(hipMalloc(&g.d_icesize, nm * sizeof(int)));
+    if (lds && !g.clusters_attr) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mw::k_ice_clusters<true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, kClusterLdsBudget));
+        g.clusters_attr = true;
+    }
+    if (launch_ice_classes(first, count, rc, timer_slot)) return 1;
+    if (timed) {
+        const int s = timer_slot + 2;
+        if (!g.ev[s][0]) { HIPCHK(hipEventCreate(&g.ev[s][0])); HIPCHK(hipEventCreate(&g.ev[s][1])); }
+        HIPCHK(hipEventRecord(g.ev[s][0], g.stream));
+    }
+    const int threads = cluster_threads(g.N);
+    int* rounds = g.d_icesum + 4 * (size_t)g.nbox;
+    if (lds)
+        hipLaunchKernelGGL((mw::k_ice_clusters<true>), dim3(1, count), dim3(threads), cluster_lds_bytes(g.N), g.stream,
+                           g.d_icecls, g.d_icenb, mask, g.d_icelabel, g.d_icesize, g.d_icesum, rounds, g.N, first - 1);
+    else
+        hipLaunchKernelGGL((mw::k_ice_clusters<false>), dim3(1, count), dim3(threads), 0, g.stream,
+                           g.d_icecls, g.d_icenb, mask, g.d_icelabel, g.d_icesize, g.d_icesum, rounds, g.N, first - 1);
+    HIPCHK(hipGetLastError());
+    g.clast[0] = first; g.clast[1] = count; g.clast[2] = lds; g.clast[3] = threads;
+    if (timed) HIPCHK(hipEventRecord(g.ev[timer_slot + 2][1], g.stream));
+    return 0;
+}
+
+int fetch_ice_clusters(int first, int count, int* label, int* summary)
+{
+    const size_t b0 = (size_t)(first - 1);
+    if (label) HIPCHK(hipMemcpyAsync(label, g.d_icelabel + b0 * g.N, sizeof(int) * g.N * count, hipMemcpyDeviceToHost, g.stream));
+    if (summary) HIPCHK(hipMemcpyAsync(summary, g.d_icesum + b0 * 4, sizeof(int) * 4 * count, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    return 0;
+}
+
 // Pair-distance histograms (mw_rdf.hip.h).  The cells are the DEVICE's (d_hmat: authoritative after volume moves), read back
 // here for the one check that needs them: r_max (1 + 1e-9) <= 1.5 x the smallest perpendicular width of every box of the call,
 // beyond which three images per axis no longer cover r_max.  Nothing is launched or written unless every box passes.
@@ -799,7 +865,8 @@ void release_all()
                     g.d_usegrid, g.d_cellid, g.d_shift, g.d_sorted, g.d_wrel, g.d_wpos, g.d_wsh, g.d_ccount, g.d_cstart, g.d_ccursor, g.d_partial,
                     g.d_cpartial, g.d_energy, g.d_counts, g.d_mimol, g.d_mtrial, g.d_meold, g.d_menew, g.d_mcnt, g.d_mperm, g.d_mdecl,
                     g.d_mwork, g.d_mom, g.d_mtot, g.d_wmom, g.d_pm, g.d_srvmomok, g.d_force, g.d_wpart, g.d_virial,
-                    g.d_iceq, g.d_icenb, g.d_icen, g.d_icecls, g.d_icecnt, g.d_icebond, g.d_rdf};
+                    g.d_iceq, g.d_icenb, g.d_icen, g.d_icecls, g.d_icecnt, g.d_icebond, g.d_rdf,
+                    g.d_icelabel, g.d_icesize, g.d_icesum};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (g.ev_srv) { (void)hipEventDestroy(g.ev_srv); g.ev_srv = nullptr; }
     if (g.h_pin) (void)hipHostFree(g.h_pin);
@@ -980,6 +1047,7 @@ static int init_impl(int device, int nwater, int nboxes, int maxneigh)
     { const char* fb = std::getenv("MW_FORCE_BRUTE_NEIGHBOURS"); g.force_brute = fb && *fb && *fb != '0'; }
     { const char* mm = std::getenv("MW_MOVE_MOMENTS"); g.move_moments = mm ? (mm[0] != '0' ? 1 : 0) : -1; }
     { const char* mp = std::getenv("MW_MODEL_PERSIST"); g.model_persist = !(mp && mp[0] == '0'); }
+    { const char* cl = std::getenv("MW_ICE_CLUSTERS_LDS"); g.clusters_lds = !(cl && cl[0] == '0'); }
     HIPCHK(hipMalloc(&g.d_partial, nb * g.nsplit_max * sizeof(double)));
     HIPCHK(hipMalloc(&g.d_cpartial, nb * g.nsplit_max * 2 * sizeof(unsigned long long)));
     HIPCHK(hipMalloc(&g.d_energy, nb * sizeof(double)));
@@ -1400,6 +1468,57 @@ int mw_ice_bonds(int ils, double rc, double* c)
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(c, g.d_icebond, n * sizeof(double), hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
+    return 0;
+}
+
+int mw_ice_clusters_launch(int first_ils, int count, double rc, int mask, int timer_slot)
+{
+    MW_LOCK;
+    if (check_live() || check_range(first_ils, count) || check_ice_rc("mw_ice_clusters_launch", rc) ||
+        check_cluster_mask("mw_ice_clusters_launch", mask)) return 1;
+    return launch_ice_clusters("mw_ice_clusters_launch", first_ils, count, rc, mask, timer_slot);
+}
+
+int mw_ice_clusters_batch(int first_ils, int count, double rc, int mask, int* label, int* summary)
+{
+    MW_LOCK;
+    if (check_live() || check_range(first_ils, count) || check_ice_rc("mw_ice_clusters_batch", rc) ||
+        check_cluster_mask("mw_ice_clusters_batch", mask)) return 1;
+    if (launch_ice_clusters("mw_ice_clusters_batch", first_ils, count, rc, mask, -1)) return 1;
+    return fetch_ice_clusters(first_ils, count, label, summary);
+}
+
+int mw_ice_clusters(int ils, double rc, int mask, int* label, int summary[4])
+{
+    MW_LOCK;
+    if (check_live() || check_box(ils) || check_ice_rc("mw_ice_clusters", rc) || check_cluster_mask("mw_ice_clusters", mask)) return 1;
+    if (launch_ice_clusters("mw_ice_clusters", ils, 1, rc, mask, -1)) return 1;
+    return fetch_ice_clusters(ils, 1, label, summary);
+}
+
+int mw_ice_clusters_plan(int nwater, int out[4])
+{
+    if (nwater < 1 || nwater > (1 << mw::kJBits)) return fail("mw_ice_clusters_plan: nwater = %d outside 1..%d", nwater, 1 << mw::kJBits);
+    if (!out) return fail("mw_ice_clusters_plan: null pointer");
+    const bool lds = cluster_lds_fits(nwater);
+    out[0] = lds;
+    out[1] = cluster_threads(nwater);
+    out[2] = lds ? (int)cluster_lds_bytes(nwater) : 0;
+    out[3] = kClusterLdsBudget / (int)(2 * sizeof(int));
+    return 0;
+}
+
+int mw_ice_clusters_last(int out[4])
+{
+    MW_LOCK;
+    if (check_live()) return 1;
+    if (!out) return fail("mw_ice_clusters_last: null pointer");
+    out[0] = g.clast[1]; out[1] = g.clast[2]; out[2] = g.clast[3]; out[3] = 0;
+    if (g.clast[1] == 0) return 0;
+    std::vector<int> r((size_t)g.clast[1]);
+    HIPCHK(hipMemcpyAsync(r.data(), g.d_icesum + 4 * (size_t)g.nbox + (g.clast[0] - 1), sizeof(int) * r.size(), hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    for (int v : r) out[3] = std::max(out[3], v);
     return 0;
 }
 

@@ -42,6 +42,7 @@ ABI_SYMBOLS = (
     "mw_model_energy_counts_total", "mw_neighbour_total",
     "mw_model_forces", "mw_model_forces_batch", "mw_model_forces_launch",
     "mw_ice_classes", "mw_ice_classes_batch", "mw_ice_classes_launch", "mw_ice_bonds",
+    "mw_ice_clusters", "mw_ice_clusters_batch", "mw_ice_clusters_launch", "mw_ice_clusters_plan", "mw_ice_clusters_last",
     "mw_rdf", "mw_rdf_batch", "mw_rdf_launch",
     "mw_local_energy", "mw_local_energy_patched", "mw_local_energy_post", "mw_local_energy_collect",
     "mw_local_energy_batch", "mw_delta_energy_batch",
@@ -149,6 +150,41 @@ ICE_RC_ANG = 3.5
 
 def _rc(rc_ang):
     return ctypes.c_double(float(rc_ang) / 0.5291772108)          # Angstrom -> bohr (constants.f90:42-43)
+
+
+#: the classes whose clusters mw_ice_clusters follows by default: ice of either stacking and its interface ("cubic" and
+#: "hexagonal" are short for the "cubic ice" and "hexagonal ice" of ICE_CLASS_NAMES)
+ICE_CLUSTER_DEFAULT = ("cubic", "hexagonal", "interfacial ice")
+
+
+def ice_cluster_mask(classes=ICE_CLUSTER_DEFAULT):
+    """The class mask of mw_ice_clusters (bit k selects class k of ICE_CLASS_NAMES) from an int mask, one class name or a
+    sequence of names; a name may drop a trailing " ice".  The engine refuses 0, bit 0 ("other") and bits above 5."""
+    if isinstance(classes, (int, np.integer)):
+        return int(classes)
+    mask = 0
+    for name in ((classes,) if isinstance(classes, str) else classes):
+        hits = [k for k, full in enumerate(ICE_CLASS_NAMES) if name == full or name + " ice" == full]
+        if not hits:
+            raise MwError(f"ice class {name!r} is none of {ICE_CLASS_NAMES}")
+        mask |= 1 << hits[0]
+    return mask
+
+
+def ice_clusters_plan(nwater):
+    """{"lds", "threads", "lds_bytes", "lds_max_nwater"} of the cluster pass for a box of ``nwater`` molecules: the engine's
+    own rule (mw_ice_clusters_plan), no device needed."""
+    L = load_library()
+    out = (ctypes.c_int * 4)()
+    if L.mw_ice_clusters_plan(int(nwater), out) != 0:
+        raise MwError(L.mw_last_error().decode())
+    return {"lds": bool(out[0]), "threads": int(out[1]), "lds_bytes": int(out[2]), "lds_max_nwater": int(out[3])}
+
+
+def cluster_sizes(label):
+    """Cluster sizes, largest first, from the labels of one box (mw_ice_clusters: 0 = not selected).  Host arithmetic only."""
+    label = np.asarray(label).ravel()
+    return np.sort(np.unique(label[label > 0], return_counts=True)[1])[::-1].astype(np.int64)
 
 
 def rdf_from_counts(hist, nwater, volume_bohr3, r_max_ang):
@@ -381,6 +417,41 @@ class EnergyModule:
         return c
 
     # -- pair-distance histogram, g(r) and n(r) (no counterpart in the reference) --------
+    # -- ice clusters: connected clusters of molecules of selected CHILL+ classes ---------
+    def ice_clusters(self, ils, classes=ICE_CLUSTER_DEFAULT, rc_ang=ICE_RC_ANG):
+        """(label int32 [nwater], summary int32 [4]) of lattice ils from the HOST's ljr, mirrored first as in ice_classes, on
+        the current list.  label[i] is 0 for a molecule whose class is not in ``classes`` (names of ICE_CLASS_NAMES or an int
+        mask), else the 1-based index of the smallest molecule of its cluster; summary = (selected molecules, clusters, size
+        of the largest cluster, its label)."""
+        self._ils(ils)
+        self._upload(ils)
+        label = np.zeros(self.nwater, dtype=np.int32)
+        summary = np.zeros(4, dtype=np.int32)
+        self._chk(self.L.mw_ice_clusters(ils, _rc(rc_ang), ice_cluster_mask(classes), _i(label), _i(summary)))
+        return label, summary
+
+    def ice_clusters_batch(self, first_ils=1, count=None, classes=ICE_CLUSTER_DEFAULT, rc_ang=ICE_RC_ANG):
+        """(label [count, nwater], summary [count, 4]) of ``count`` boxes from the positions and cells the DEVICE holds, one
+        launch per pass."""
+        count = self.num_lattices - first_ils + 1 if count is None else count
+        self._ils(first_ils), self._ils(first_ils + count - 1)
+        label = np.zeros((count, self.nwater), dtype=np.int32)
+        summary = np.zeros((count, 4), dtype=np.int32)
+        self._chk(self.L.mw_ice_clusters_batch(first_ils, count, _rc(rc_ang), ice_cluster_mask(classes), _i(label), _i(summary)))
+        return label, summary
+
+    def ice_clusters_launch(self, first_ils, count, classes=ICE_CLUSTER_DEFAULT, rc_ang=ICE_RC_ANG, timer_slot=-1):
+        """The passes of ice_clusters_batch, results left on the device; timer_slot >= 0: event timers timer_slot and
+        timer_slot + 1 (the classification passes) and timer_slot + 2 (the cluster pass)."""
+        self._chk(self.L.mw_ice_clusters_launch(first_ils, count, _rc(rc_ang), ice_cluster_mask(classes), timer_slot))
+
+    def ice_clusters_last(self):
+        """{"boxes", "lds", "threads", "rounds"} of the last cluster launch (rounds: the most hook / compress rounds any of its
+        boxes took)."""
+        out = (ctypes.c_int * 4)()
+        self._chk(self.L.mw_ice_clusters_last(out))
+        return {"boxes": int(out[0]), "lds": bool(out[1]), "threads": int(out[2]), "rounds": int(out[3])}
+
     def rdf_counts(self, ils, r_max_ang, nbins):
         """int64 [nbins]: the pair-distance histogram of lattice ils (mw_rdf: ordered pairs with all periodic images inside
         ``r_max_ang``, Angstrom) from the positions and the cell the DEVICE holds."""

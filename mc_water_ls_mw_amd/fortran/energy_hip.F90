@@ -47,6 +47,7 @@ module energy
   public :: compute_model_forces      ! extension: forces and virial of the full-box energy
   public :: compute_ice_classes       ! extension: CHILL+ ice structure class of every molecule
   public :: compute_rdf               ! extension: pair-distance histogram of a lattice, for g(r) and n(r)
+  public :: compute_ice_clusters      ! extension: connected clusters of molecules of selected CHILL+ classes
 
   ! current energy due to the model Hamiltonian (host array, written by callers too)
   real(kind=dp),allocatable,dimension(:),save :: model_energy
@@ -159,6 +160,13 @@ module energy
        real(c_double),value :: r_max
        integer(c_long_long),intent(out) :: hist(*)
      end function mw_rdf
+     integer(c_int) function mw_ice_clusters(ils,rc,mask,label,summary) bind(C,name="mw_ice_clusters")
+       import :: c_int,c_double
+       integer(c_int),value :: ils,mask
+       real(c_double),value :: rc
+       integer(c_int),intent(out) :: label(*)
+       integer(c_int),intent(out) :: summary(4)
+     end function mw_ice_clusters
      integer(c_int) function mw_local_energy_patched(ils,imol,r_imol,imol_prev,r_prev,e) &
           bind(C,name="mw_local_energy_patched")
        import :: c_int,c_double
@@ -480,6 +488,30 @@ contains
     call mw_check(mw_rdf(int(ils,c_int),real(r_max,c_double),int(nbins,c_int),hist),'compute_rdf')
     return
   end subroutine compute_rdf
+
+  subroutine compute_ice_clusters(ils,rc,mask,label,summary)
+    !------------------------------------------------------------------------------!
+    ! Extension: connected clusters of the molecules of lattice ils whose CHILL+    !
+    ! class (compute_ice_classes, same rc in bohr) is in mask -- bit k selects      !
+    ! class k, 1 <= k <= 5; 14 = cubic + hexagonal + interfacial ice is usual --    !
+    ! from the host's ljr, mirrored first, on the current list.  Two selected       !
+    ! molecules are bonded iff one is among the other's four CHILL+ neighbours.     !
+    ! label(imol) = 0 where imol is not selected, else the smallest molecule of its !
+    ! cluster; summary = selected molecules, clusters, size of the largest cluster, !
+    ! label of the largest cluster (ties: the smallest label).                      !
+    !------------------------------------------------------------------------------!
+    use model, only : ljr
+    implicit none
+    integer,intent(in) :: ils,mask
+    real(kind=dp),intent(in) :: rc
+    integer(c_int),intent(out) :: label(:)
+    integer(c_int),intent(out) :: summary(4)
+    call mw_check(mw_upload_positions(int(ils,c_int),ljr(:,1,:,ils)),'compute_ice_clusters')
+    last_imol(ils) = 0
+    stale(ils) = .false.
+    call mw_check(mw_ice_clusters(int(ils,c_int),real(rc,c_double),int(mask,c_int),label,summary),'compute_ice_clusters')
+    return
+  end subroutine compute_ice_clusters
 
   subroutine compute_neighbours(ils)
     !------------------------------------------------------------------------------!

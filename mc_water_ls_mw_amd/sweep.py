@@ -12,6 +12,8 @@ import math
 
 import numpy as np
 
+from .energy import ICE_CLUSTER_DEFAULT
+
 KB = 1.0 / 3.1577465e5          # constants.f90:39, Hartree / Kelvin
 _dp = ctypes.POINTER(ctypes.c_double)
 
@@ -299,6 +301,16 @@ class WalkerFarm:
         self.sync_cells()
         _, counts = self.em.ice_classes_batch(1, self.em.num_lattices, rc_ang)
         return counts.reshape(self.nwalkers, self.nlat, 6) / float(self.em.nwater)
+
+    def largest_ice_clusters(self, classes=ICE_CLUSTER_DEFAULT, rc_ang=3.5):
+        """Size of the largest connected cluster of molecules of the CHILL+ classes ``classes`` (default
+        energy.ICE_CLUSTER_DEFAULT: cubic, hexagonal and interfacial ice) in every lattice of every walker, an int array
+        (nwalkers, nlat), from the positions and cells the device holds (the cells read back through :meth:`sync_cells`
+        first); one batch over all boxes.  The stricter validity check beside :meth:`ice_fractions`: an Ih lattice is
+        still Ih only while its hexagonal molecules form one cluster of nearly nwater."""
+        self.sync_cells()
+        _, summary = self.em.ice_clusters_batch(1, self.em.num_lattices, classes, rc_ang)
+        return summary[:, 2].reshape(self.nwalkers, self.nlat).astype(np.int64)
 
     def rdf(self, r_max_ang=10.0, nbins=200):
         """(r_ang [nbins], g [nlat, nbins], n [nlat, nbins]): the radial distribution function and the running coordination
