@@ -4,44 +4,38 @@
 extern "C" {
 
 // The instantiations of the Monte Carlo driver: lattices per walker x residency (0: positions and rows from global memory /
-// L2, 1: positions in LDS, 2: positions and list rows in LDS) x with / without volume moves; and, for walkers whose data
-// stay in global memory, look-ahead over 2 or 4 moves (wavefronts per workgroup = lattices x look-ahead).
+// L2, 1: positions in LDS, 2: positions and list rows in LDS) x with / without volume moves; and look-ahead over 2 or 4 moves
+// (wavefronts per workgroup = lattices x look-ahead) for every residency, 8 and 6 for one kind of walker each.
+// X(lattices, look-ahead, positions in LDS, rows in LDS): each is built without and with volume moves.  (The order of this list is
+// the order of the kernels in the code object.)
+#define MW_SWEEP_BUILDS(X) \
+    X(1, 1, false, false) X(1, 1, true, false) X(1, 1, true, true) \
+    X(2, 1, false, false) X(2, 1, true, false) X(2, 1, true, true) \
+    /* look-ahead 2 / 4, residency 0 */ \
+    X(1, 2, false, false) X(1, 4, false, false) X(2, 2, false, false) X(2, 4, false, false) \
+    /* the same for walkers entirely in LDS (residency 2): the reference's own handful of 48-molecule walkers is a handful of */ \
+    /* chains, and their speed is the chain's */ \
+    X(1, 2, true, true) X(1, 4, true, true) X(2, 2, true, true) X(2, 4, true, true) \
+    /* ... and for the sizes in between (positions in LDS, rows in global memory) */ \
+    X(1, 2, true, false) X(1, 4, true, false) X(2, 2, true, false) X(2, 4, true, false) \
+    /* eight moves in flight: ONE lattice, walkers in global memory (a 4096-molecule box or a few of them) */ \
+    X(1, 8, false, false) \
+    /* six moves in flight: TWO lattices entirely in LDS (twelve wavefronts of the 168-register builds fill a CU: one walker per */ \
+    /* CU -- the reference's handful of 48-molecule walkers) */ \
+    X(2, 6, true, true)
+
 static const void* sweep_kernel(int nlat, int residency, bool withvol, int spec)
 {
-#define MW_SWEEP_K(L, SP, P, R, V) reinterpret_cast<const void*>(&mw::k_sweep<L, SP, P, R, V>)
-    static const void* const tab[2][3][2] = {
-        {{MW_SWEEP_K(1, 1, false, false, false), MW_SWEEP_K(1, 1, false, false, true)},
-         {MW_SWEEP_K(1, 1, true, false, false),  MW_SWEEP_K(1, 1, true, false, true)},
-         {MW_SWEEP_K(1, 1, true, true, false),   MW_SWEEP_K(1, 1, true, true, true)}},
-        {{MW_SWEEP_K(2, 1, false, false, false), MW_SWEEP_K(2, 1, false, false, true)},
-         {MW_SWEEP_K(2, 1, true, false, false),  MW_SWEEP_K(2, 1, true, false, true)},
-         {MW_SWEEP_K(2, 1, true, true, false),   MW_SWEEP_K(2, 1, true, true, true)}}};
-    static const void* const ahead[2][2][2] = {       // [lattices][look-ahead 2 / 4][volume moves], residency 0
-        {{MW_SWEEP_K(1, 2, false, false, false), MW_SWEEP_K(1, 2, false, false, true)},
-         {MW_SWEEP_K(1, 4, false, false, false), MW_SWEEP_K(1, 4, false, false, true)}},
-        {{MW_SWEEP_K(2, 2, false, false, false), MW_SWEEP_K(2, 2, false, false, true)},
-         {MW_SWEEP_K(2, 4, false, false, false), MW_SWEEP_K(2, 4, false, false, true)}}};
-    static const void* const ahead_lds[2][2][2] = {   // the same for walkers entirely in LDS (residency 2): the reference's own handful
-        {{MW_SWEEP_K(1, 2, true, true, false), MW_SWEEP_K(1, 2, true, true, true)},          // of 48-molecule walkers is a handful of
-         {MW_SWEEP_K(1, 4, true, true, false), MW_SWEEP_K(1, 4, true, true, true)}},         // chains, and their speed is the chain's
-        {{MW_SWEEP_K(2, 2, true, true, false), MW_SWEEP_K(2, 2, true, true, true)},
-         {MW_SWEEP_K(2, 4, true, true, false), MW_SWEEP_K(2, 4, true, true, true)}}};
-    static const void* const ahead_pos[2][2][2] = {   // ... and for the sizes in between (positions in LDS, rows in global memory)
-        {{MW_SWEEP_K(1, 2, true, false, false), MW_SWEEP_K(1, 2, true, false, true)},
-         {MW_SWEEP_K(1, 4, true, false, false), MW_SWEEP_K(1, 4, true, false, true)}},
-        {{MW_SWEEP_K(2, 2, true, false, false), MW_SWEEP_K(2, 2, true, false, true)},
-         {MW_SWEEP_K(2, 4, true, false, false), MW_SWEEP_K(2, 4, true, false, true)}}};
-    static const void* const ahead8[2] = {            // eight moves in flight: ONE lattice, walkers in global memory (a 4096-molecule box or a few of them)
-        MW_SWEEP_K(1, 8, false, false, false), MW_SWEEP_K(1, 8, false, false, true)};
-    static const void* const ahead6[2] = {            // six moves in flight: TWO lattices entirely in LDS (twelve wavefronts of the 168-register builds fill a CU:
-        MW_SWEEP_K(2, 6, true, true, false), MW_SWEEP_K(2, 6, true, true, true)};          // one walker per CU -- the reference's handful of 48-molecule walkers)
+    struct Build { int nlat, spec; bool ldspos, ldslist, withvol; const void* kern; };
+#define MW_SWEEP_K(L, SP, P, R) {L, SP, P, R, false, reinterpret_cast<const void*>(&mw::k_sweep<L, SP, P, R, false>)}, \
+                                {L, SP, P, R, true, reinterpret_cast<const void*>(&mw::k_sweep<L, SP, P, R, true>)},
+    static const Build builds[] = {MW_SWEEP_BUILDS(MW_SWEEP_K)};
 #undef MW_SWEEP_K
-    if (spec == 8) return (nlat == 1 && residency == 0) ? ahead8[withvol ? 1 : 0] : nullptr;
-    if (spec == 6) return (nlat == 2 && residency == 2) ? ahead6[withvol ? 1 : 0] : nullptr;
-    if (spec > 1 && residency == 0) return ahead[nlat - 1][spec == 4 ? 1 : 0][withvol ? 1 : 0];
-    if (spec > 1 && residency == 1) return ahead_pos[nlat - 1][spec == 4 ? 1 : 0][withvol ? 1 : 0];
-    if (spec > 1 && residency == 2) return ahead_lds[nlat - 1][spec == 4 ? 1 : 0][withvol ? 1 : 0];
-    return tab[nlat - 1][residency][withvol ? 1 : 0];
+    // 8 and 6 only where they are built; any other look-ahead is 4 or 2
+    const int ahead = (spec == 8 || spec == 6) ? spec : (spec > 1 ? (spec == 4 ? 4 : 2) : 1);
+    for (const Build& b : builds)
+        if (b.nlat == nlat && b.spec == ahead && b.ldspos == (residency >= 1) && b.ldslist == (residency == 2) && b.withvol == withvol) return b.kern;
+    return nullptr;
 }
 
 int mw_sweep_configure(int nlat, double beta, double max_trans, int nbins, int eta_interp, int start_bin, int end_bin,

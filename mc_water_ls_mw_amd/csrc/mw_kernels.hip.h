@@ -19,7 +19,7 @@
 //   mw_neighbours.hip.h   neighbour-list builders
 //   mw_full_energy.hip.h  full-box energy
 //   mw_move_energy.hip.h  local energy / fused trial-move energy
-//   mw_sweep.hip.h        device-resident Monte Carlo driver
+//   mw_sweep.hip.h        device-resident Monte Carlo driver (k_sweep; includes mw_sweep_common / _volume / _decide.hip.h)
 //   mw_forces.hip.h       forces and virial of the full-box energy
 //   mw_ice.hip.h          per-molecule ice structure classes (CHILL+)
 //   mw_rdf.hip.h          pair-distance histograms for g(r) and n(r)

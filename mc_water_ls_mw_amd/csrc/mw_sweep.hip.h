@@ -3,606 +3,11 @@
 // mc_update_wl_bins, mc_lattice_switch of mc_moves.F90 for many independent walkers.
 #pragma once
 
-#include "mw_common.hip.h"
-#include "mw_full_energy.hip.h"
-#include "mw_move_energy.hip.h"
+#include "mw_sweep_common.hip.h"
+#include "mw_sweep_volume.hip.h"
+#include "mw_sweep_decide.hip.h"
 
 namespace mw {
-
-// =====================================================================================
-// Device-resident translation-move driver: mc_water_translation
-// (mc_moves.F90:966-1213) with eta_weight (:893-964) and mu_to_bin (:2187-2215), for many
-// independent walkers at once.  One workgroup per walker -- one wavefront per lattice -- runs its
-// Markov chain move after move: pick a molecule, draw the displacement in the active lattice, map
-// it through fractional coordinates into the partner lattice (:1042-1066), fused old/new local
-// energy in each lattice (move_energy_wave, the lattices side by side), update the order parameter
-// mu and the multicanonical weights' contribution, accept or revert (:1145-1209).  The caller-side
-// bookkeeping of model_energy (:1013-1016,1087,1190) is done here on the per-box energies.
-// Random numbers: Philox4x32-10, counter (move lo, move hi, walker, call), key = seed -- the same
-// stream as the oracle's mwo_move_uniforms.
-//   grid = walkers in the launch, block = 64 x lattices
-// =====================================================================================
-struct SweepParams {
-    double beta, max_trans;
-    double r_pos, a_pos, r_neg, a_neg, mu_lo, mu_hi;
-    int nlat, nbins, eta_interp, start_bin, end_bin, pad;
-    // the rest of a translation-only mc_cycle (all off by default)
-    int record, samplerun, always_switch, npt;      // mc_update_wl_bins active / fixed weights / switch after every move / ensemble
-    double av_binwidth, wl_factor, log_unbiased_norm, pressure;
-    double transP, dv_max;                          // move-type threshold (mc_moves.F90:157-166), max cell-element change
-    // leshift (userparams.f90:41): ref_enthalpy(1) - ref_enthalpy(2), 0 when off (main.f90:146-150,173; mc_moves.F90:1371,1567-1584)
-    double dref;
-    // wl_swetnam (mc_moves.F90:1636-1653): the increment follows the histogram's r.m.s. deviation from flat, move by move
-    int swetnam, dd;                                // dd: parallel_strategy = 'dd' (window per walker, mc_moves.F90:181-210,659-709)
-    double wl_alpha, orig_wl_factor, mu_min, mu_max;
-    int eq_cycles, in_window;                       // dd: equilibration length (cycles); in_window: this walker's flag (filled per walker)
-    // the reference's -DMINU build (mc_moves.F90:1119-1140,1168-1170,1385-1401,1426-1429): an accepted move also takes the
-    // walker to the lattice of lower enthalpy; ref1/ref2 = ref_enthalpy(1:2) under leshift, 0 otherwise
-    int minu, pad_minu;
-    double ref1, ref2;
-};
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-__device__ __forceinline__ double u53(uint32_t a, uint32_t b)
-{
-    return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) * (1.0 / 9007199254740992.0);
-}
-
-// -------------------------------------------------------------------------------------
-// Order parameter -> bin -> weight, LANE-PARALLEL.  These are scalar computations of the host program (a log, three
-// divisions, an exp per call) and a wavefront has no scalar double-precision unit: evaluated one after the other by all
-// 64 lanes they cost more vector instructions per move than one lattice's whole energy evaluation (profiles/r03a: 2200
-// VALU instructions per two-lattice move with the Wang-Landau update and a switch attempt, 1170 of them energy).  Here
-// every value of mu a move needs -- the trial value, the value a rejection restores, the current one -- sits in its own
-// lane and ONE instruction stream serves them all; likewise the move's exponentials.
-// -------------------------------------------------------------------------------------
-struct MuGridDev {                       // per walker, wave-uniform
-    double c_pos, c_neg, ilr_pos, ilr_neg, mu_lo, mu_hi;       // c = (1 - r) / a, ilr = 1 / log(r) of the two geometric bin progressions
-    int nbins, start_bin, end_bin, eta_interp, in_window;
-};
-
-// mc_moves.F90:2187-2215, one mu per lane: bin = nbins/2 + 2 + int(log(1 - (mu - 0.5)(1 - r)/a) / log r) on the positive side.  The
-// two divisions are multiplications by per-walker constants and the logarithm is the engine's own (mw_common.hip.h) -- 45 vector
-// instructions where the expression as written costs 220; the bin differs from the reference's only for a mu within ~1e-15
-// (relative) of a bin boundary, where two libm implementations differ as well.
-__device__ __forceinline__ int lane_mu_to_bin(const MuGridDev& g, double mu)
-{
-    const double a = fabs(mu);
-    const bool pos = mu > 0.0;
-    const double c = pos ? g.c_pos : g.c_neg, ilr = pos ? g.ilr_pos : g.ilr_neg;
-    const double arg = __builtin_fma(-(a - 0.5), c, 1.0);
-    const int q = (int)(fast_log_pos(arg) * ilr);
-    return a <= 0.5 ? g.nbins / 2 + 1 : (pos ? g.nbins / 2 + 2 + q : g.nbins / 2 - q);
-}
-
-// eta_weight (mc_moves.F90:893-964) for one mu per lane, bin k already known; w / mb / bw: 0-based tables in LDS.
-// The four interpolation branches of the reference are one expression with selected indices:
-//   eta = w(base) + (mu - mu_bin(base)) * 2 (w(hi) - w(lo)) / (binwidth(hi) + binwidth(lo)),   hi = lo + 1
-__device__ __forceinline__ double lane_eta(const MuGridDev& g, const double* w, const double* __restrict__ mb,
-                                           const double* __restrict__ bw, double mu, int k)
-{
-    const int nb = g.nbins;
-    const int kc = k < 1 ? 1 : (k > nb ? nb : k);               // (a bin outside the table only with mu outside the range: not used then)
-    const bool up = (kc == g.start_bin) || (kc != g.end_bin && mu > mb[kc - 1]);
-    int hi = up ? kc + 1 : kc;
-    hi = hi > nb ? nb : (hi < 2 ? 2 : hi);
-    const int lo = hi - 1;
-    const int base = (up || kc == g.end_bin) ? kc : (kc > 1 ? kc - 1 : 1);
-    double val = w[kc - 1];
-    if (g.eta_interp) val = w[base - 1] + (mu - mb[base - 1]) * (2.0 * (w[hi - 1] - w[lo - 1]) / (bw[hi - 1] + bw[lo - 1]));
-    // 'dd' walkers that have not reached their window yet carry no weight: the reference returns there without
-    // assigning the function result (:913); 0 is what its comment asks for ("don't want to penalise walkers")
-    val = (mu < g.mu_lo || mu > g.mu_hi) ? 1.7976931348623157e308 : val;      // huge(1.0_dp)
-    return g.in_window ? val : 0.0;
-}
-
-#define MW_HM(m, r, c) ((m)[((c) - 1) * 3 + ((r) - 1)])     // Fortran (r,c) of a column-major 3x3
-__device__ __forceinline__ void dev_recipmatrix(const double* __restrict__ h, double rc[9])   // util.f90:43-77
-{
-    MW_HM(rc,1,1) = MW_HM(h,2,2)*MW_HM(h,3,3) - MW_HM(h,2,3)*MW_HM(h,3,2);
-    MW_HM(rc,1,2) = MW_HM(h,2,3)*MW_HM(h,3,1) - MW_HM(h,2,1)*MW_HM(h,3,3);
-    MW_HM(rc,1,3) = MW_HM(h,2,1)*MW_HM(h,3,2) - MW_HM(h,2,2)*MW_HM(h,3,1);
-    MW_HM(rc,2,1) = MW_HM(h,1,3)*MW_HM(h,3,2) - MW_HM(h,1,2)*MW_HM(h,3,3);
-    MW_HM(rc,2,2) = MW_HM(h,1,1)*MW_HM(h,3,3) - MW_HM(h,1,3)*MW_HM(h,3,1);
-    MW_HM(rc,2,3) = MW_HM(h,1,2)*MW_HM(h,3,1) - MW_HM(h,1,1)*MW_HM(h,3,2);
-    MW_HM(rc,3,1) = MW_HM(h,1,2)*MW_HM(h,2,3) - MW_HM(h,1,3)*MW_HM(h,2,2);
-    MW_HM(rc,3,2) = MW_HM(h,1,3)*MW_HM(h,2,1) - MW_HM(h,1,1)*MW_HM(h,2,3);
-    MW_HM(rc,3,3) = MW_HM(h,1,1)*MW_HM(h,2,2) - MW_HM(h,1,2)*MW_HM(h,2,1);
-    const double vol = MW_HM(h,1,1)*MW_HM(rc,1,1) + MW_HM(h,1,2)*MW_HM(rc,1,2) + MW_HM(h,1,3)*MW_HM(rc,1,3);
-    const double f = 2.0 * 3.141592653589793238462643383279502884197 / vol;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) rc[i] *= f;
-}
-
-// Diagnostic build only (-DMW_SWEEP_STAMPS, tools/sweep_stamps.py): cycles of walker 0's first wavefront per phase of a round,
-// summed over the launch into g_sweep_stamps[0..15] (mw_move_energy.hip.h holds the array and the stages of one evaluation).
-#ifdef MW_SWEEP_STAMPS
-#define MW_SW_NOW() ((blockIdx.x == 0 && wv == 0) ? (unsigned long long)clock64() : 0ull)
-#define MW_SW_ACC(k, d) do { if (blockIdx.x == 0 && wv == 0 && lane == 0) g_sweep_stamps[k] += (d); } while (0)
-#else
-#define MW_SW_NOW() 0ull
-#define MW_SW_ACC(k, d) do { } while (0)
-#endif
-
-#ifndef MW_BIG_WHEN
-#define MW_BIG_WHEN ((SPEC > 1) ? 1 : 0)      // when the moments of walkers in global memory are asked for (move_energy_mom_wave: WHEN)
-#endif
-constexpr int kSweepQCap = 9;                             // in-range queue of a volume move's full-box energy: sized to fit the scratch record
-// -------------------------------------------------------------------------------------
-// Volume move of one walker by its wavefront: mc_volume (mc_moves.F90:1216-1534; ref_ljr,
-// which only chain synchronisation reads, is not carried).  Rare (probability ~1/N per move), so it is an
-// out-of-line function: one symmetric hmatrix element of both lattices changes, every position is rescaled
-// through fractional coordinates (lanes over molecules), image vectors are rebuilt on the device in the
-// reference's order and arithmetic, and the full-box energies are recomputed by the wavefront WITH THE
-// EXISTING LISTS (atom_energy over the slot-major list); on rejection everything is put back the way the
-// reference does it (positions mapped back through the NEW reciprocal matrix, :1413-1506).
-// -------------------------------------------------------------------------------------
-struct VolCtx {
-    double* pos_g;            // global positions of the walker's first box
-    double* spos;             // LDS positions [L][N][3] or nullptr
-    double* shmat;            // LDS hmatrix   [2][9]
-    double* srecip;           // LDS recip     [2][9]
-    double* svol;             // LDS volume    [2]
-    double* sbk;              // LDS backup of a volume move's old cells [2][27]
-    double* siv;              // LDS image vectors [L][ivcap][3]
-    int* sniv;                // LDS nivect    [2]
-    double* hmat_g;           // global mirrors of the above, walker's first box
-    double* vol_g;
-    double* ivect_g;
-    int* nivect_g;
-    const uint32_t* list_g;   // slot-major list (columns in k_list_order's order), walker's first box
-    const int* order_g;       // molecule of each column
-    const int* nns_g;         // row length of each column
-    const int* cmax_g;        // longest row per group of 64 columns
-    uint32_t* queue;          // this lane's column of an LDS queue [kSweepQCap + 1][64]
-    const unsigned short* srow;   // LDS list rows [L][N][rstride] (16-bit entries) and row lengths [L][N] of walkers entirely in LDS, else nullptr
-    const unsigned char* snn;
-    int rstride;
-    double* mom_trial;        // where a volume move leaves the moments of the trial cell, [L][N][kMomStride], or nullptr
-    unsigned* inmask;         // SPLIT builds (volume_move_wg): per molecule the row slots in range, [L][N]
-    double* rec;              // ... and the in-range neighbours' {dx, dy, dz, 1/r, e1, g}, [L][N][kSplitQ][6]
-    int N, S, ivcap, L;
-};
-constexpr int kSplitQ = 12;   // in-range neighbours per molecule the split evaluation has room for (more: the one-wavefront routine)
-
-// compute_ivects (molint.F90:174-217) for one lattice, lanes over vectors; returns nivect or -1
-__device__ __forceinline__ int dev_compute_ivects(const double* __restrict__ h, double* __restrict__ siv_l,
-                                                  double* __restrict__ iv_g, int ivcap, int lane)
-{
-#pragma clang fp contract(off)
-    const double rc = kSmallA * kSigma;
-    const int im = (int)floor(rc / sqrt(h[0] * h[0] + h[1] * h[1] + h[2] * h[2])) + 1;       // :189-191
-    const int jm = (int)floor(rc / sqrt(h[3] * h[3] + h[4] * h[4] + h[5] * h[5])) + 1;
-    const int km = (int)floor(rc / sqrt(h[6] * h[6] + h[7] * h[7] + h[8] * h[8])) + 1;
-    const int w1 = 2 * jm + 1, w2 = 2 * km + 1;
-    const int n = (2 * im + 1) * w1 * w2;                                                    // :193
-    if (n > ivcap) return -1;
-    const int central = (im * w1 + jm) * w2 + km;
-    for (int k = lane; k < n; k += 64) {
-        double vx = 0.0, vy = 0.0, vz = 0.0;                                                 // :197 central cell first
-        if (k > 0) {
-            const int lin = (k - 1 < central) ? k - 1 : k;                                   // loop order of :200-213
-            const int kc = lin % w2 - km, jc = (lin / w2) % w1 - jm, ic = lin / (w2 * w1) - im;
-            const double sx0 = (double)ic * h[0], sx1 = (double)ic * h[1], sx2 = (double)ic * h[2];
-            const double sy0 = (double)jc * h[3], sy1 = (double)jc * h[4], sy2 = (double)jc * h[5];
-            const double sz0 = (double)kc * h[6], sz1 = (double)kc * h[7], sz2 = (double)kc * h[8];
-            vx = (sx0 + sy0) + sz0; vy = (sx1 + sy1) + sz1; vz = (sx2 + sy2) + sz2;          // :208
-        }
-        siv_l[3 * k] = vx; siv_l[3 * k + 1] = vy; siv_l[3 * k + 2] = vz;
-        iv_g[3 * k] = vx; iv_g[3 * k + 1] = vy; iv_g[3 * k + 2] = vz;
-    }
-    return n;
-}
-
-__device__ __forceinline__ double dev_det3(const double* m)                                   // util.f90:16-41
-{
-    double det = MW_HM(m,1,1) * (MW_HM(m,2,2) * MW_HM(m,3,3) - MW_HM(m,2,3) * MW_HM(m,3,2));
-    det = det - MW_HM(m,1,2) * (MW_HM(m,2,1) * MW_HM(m,3,3) - MW_HM(m,2,3) * MW_HM(m,3,1));
-    det = det + MW_HM(m,1,3) * (MW_HM(m,2,1) * MW_HM(m,3,2) - MW_HM(m,2,2) * MW_HM(m,3,1));
-    return det;
-}
-
-// ljr += (H_new * (recip . ljr / 2 pi) - ljr), lanes over molecules (mc_moves.F90:1288-1316)
-// (LDSPOS at compile time: a pointer chosen at run time between LDS and global memory makes every access through it a FLAT one --
-//  the full-box energy's position gathers, hundreds per volume move, among them)
-template <bool LDSPOS>
-__device__ __forceinline__ void dev_rescale(const VolCtx& c, int l, const double* recip, const double* hnew, int lane)
-{
-    const double invPi = 1.0 / 3.141592653589793238462643383279502884197;
-    double* Pg = c.pos_g + (size_t)l * c.N * 3;
-    double* Ps = c.spos + (size_t)l * c.N * 3;
-    for (int i = lane; i < c.N; i += 64) {
-        const double* p = LDSPOS ? Ps + 3 * i : Pg + 3 * i;
-        const double o0 = p[0], o1 = p[1], o2 = p[2];
-        double s0 = MW_HM(recip,1,1) * o0 + MW_HM(recip,2,1) * o1 + MW_HM(recip,3,1) * o2;
-        double s1 = MW_HM(recip,1,2) * o0 + MW_HM(recip,2,2) * o1 + MW_HM(recip,3,2) * o2;
-        double s2 = MW_HM(recip,1,3) * o0 + MW_HM(recip,2,3) * o1 + MW_HM(recip,3,3) * o2;
-        s0 = s0 * 0.5 * invPi; s1 = s1 * 0.5 * invPi; s2 = s2 * 0.5 * invPi;
-        double t0 = MW_HM(hnew,1,1) * s0 + MW_HM(hnew,1,2) * s1 + MW_HM(hnew,1,3) * s2;
-        double t1 = MW_HM(hnew,2,1) * s0 + MW_HM(hnew,2,2) * s1 + MW_HM(hnew,2,3) * s2;
-        double t2 = MW_HM(hnew,3,1) * s0 + MW_HM(hnew,3,2) * s1 + MW_HM(hnew,3,3) * s2;
-        t0 = t0 - o0; t1 = t1 - o1; t2 = t2 - o2;
-        const double n0 = o0 + t0, n1 = o1 + t1, n2 = o2 + t2;
-        Pg[3 * i] = n0; Pg[3 * i + 1] = n1; Pg[3 * i + 2] = n2;
-        if constexpr (LDSPOS) { Ps[3 * i] = n0; Ps[3 * i + 1] = n1; Ps[3 * i + 2] = n2; }
-    }
-}
-
-// compute_model_energy of lattice l by one wavefront (value in every lane).  `mom_l` (walkers entirely in LDS only): every
-// molecule's moments too, [N][kMomStride] -- what the translations' moment path reads (move_energy_mom_wave)
-// (BATCH4: the distance tests' gathers four at a time -- for the look-ahead builds, which have the registers)
-template <bool LDSPOS, bool BATCH4 = false>
-__device__ __forceinline__ double dev_wave_model_energy(const VolCtx& c, int l, int lane, double* __restrict__ mom_l = nullptr)
-{
-    const double* Pg = c.pos_g + (size_t)l * c.N * 3;
-    const double* Ps = c.spos + (size_t)l * c.N * 3;
-    const double* IVl = c.siv + (size_t)l * c.ivcap * 3;
-    const uint32_t* Lg = c.list_g + (size_t)l * c.S * c.N;
-    const int* ORD = c.order_g + (size_t)l * c.N;
-    const int* NNS = c.nns_g + (size_t)l * c.N;
-    const int* CM = c.cmax_g + (size_t)l * ((c.N + 63) >> 6);
-    auto getiv = [&](int k, double& x, double& y, double& z) { x = IVl[3 * k]; y = IVl[3 * k + 1]; z = IVl[3 * k + 2]; };
-    auto getpos = [&](int j, double& x, double& y, double& z) {
-        const double* p = LDSPOS ? Ps + 3 * (size_t)j : Pg + 3 * (size_t)j;
-        x = p[0]; y = p[1]; z = p[2];
-    };
-    double esum = 0.0;
-    if (c.srow) {
-        // a walker entirely in LDS: its rows are there too (molecule-major, 16-bit entries) -- one lane per molecule, no list read
-        // from global memory (the slot-major list cost three dependent global round trips of ~1.5 us each: 9 of a volume move's 19 us)
-        uint32_t cur[8];
-        for (int base = 0; base < c.N; base += 64) {
-            const int mol = base + lane;
-            const bool act = mol < c.N;
-            const int n = act ? (int)c.snn[l * c.N + mol] : 0;
-            const int nmax = __builtin_amdgcn_readfirstlane(wave_max_i(n));
-            const unsigned short* row = c.srow + ((size_t)l * c.N + (act ? mol : 0)) * c.rstride;
-            auto ent = [&](int s) -> uint32_t { const uint32_t e = s < n ? (uint32_t)row[s] : 0u; return (e & 63u) | ((e >> 6) << kJBits); };
-            AtomSum a = atom_energy<64, BATCH4, true, kSweepQCap>(ListRsrc(), kNoColumn, kNoColumn, act ? mol : 0, n, nmax, 0, c.N, c.S, c.queue, getpos, getiv, cur,
-                                                                 (mom_l && act) ? mom_l + (size_t)mol * kMomStride : nullptr, ent);
-            if (act) esum += a.e;
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) esum += __shfl_xor(esum, off, 64);
-        return esum;
-    }
-    const ListRsrc rs = list_rsrc(Lg, c.N, c.S);
-    uint32_t cur[8];
-    int n_cur = 0, mol = 0;
-    uint32_t col = kNoColumn;
-    if (lane < c.N) { col = (uint32_t)lane * 4u; n_cur = NNS[lane]; mol = ORD[lane]; }
-    for (int base = 0; base < c.N; base += 64) {                 // wave-uniform: one group of 64 list columns per pass
-        const bool act = col != kNoColumn;
-        const int tn = base + 64 + lane;
-        uint32_t col_next = kNoColumn;
-        int n_next = 0, mol_next = 0;
-        if (tn < c.N) { col_next = (uint32_t)tn * 4u; n_next = NNS[tn]; mol_next = ORD[tn]; }
-        const int cm = __builtin_amdgcn_readfirstlane(CM[base >> 6]);
-        AtomSum a = atom_energy<64, false, true, kSweepQCap>(rs, col, col_next, mol, act ? (n_cur & 0xff) : 0, cm & 0xff, cm >> 8, c.N, c.S, c.queue, getpos, getiv, cur,
-                                                             (mom_l && act) ? mom_l + (size_t)mol * kMomStride : nullptr);
-        if (act) esum += a.e;
-        n_cur = n_next; mol = mol_next; col = col_next;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) esum += __shfl_xor(esum, off, 64);
-    return esum;
-}
-
-// -------------------------------------------------------------------------------------
-// The workgroup of a walker: one wavefront per lattice.  Each wavefront evaluates ITS lattice (the fused old/new local
-// energy of a translation, the rescaled box of a volume move); wavefront 0 then takes the move's decision -- order
-// parameter, weights, Metropolis test, Wang-Landau update, lattice switch -- and hands {accepted, active lattice} back.
-// Two workgroup barriers per move for two lattices, none for one.
-// -------------------------------------------------------------------------------------
-template <int NW>                                           // NW = wavefronts in the workgroup
-__device__ __forceinline__ void wg_sync()
-{
-    if constexpr (NW == 1) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    } else {
-        __syncthreads();
-    }
-}
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-// moves per batch of uniforms (Philox calls are lanes of one pass): 16, or 8 for the builds with volume moves -- 512 B of LDS that an
-// NPT walker of the reference's examples does not have (sweep_lds); the smaller batch costs the translation-only build ~2 %
-__host__ __device__ constexpr int sweep_batch(bool withvol, int spec = 1) { return spec > (withvol ? 8 : 16) ? spec : (withvol ? 8 : 16); }
-constexpr unsigned kSweepScratch = (unsigned)((sizeof(WaveScratch) + 15) & ~(size_t)15);
-constexpr unsigned kSweepScratchVol = (unsigned)(((kSweepQCap + 1) * 64 * sizeof(uint32_t)) > kSweepScratch ? ((kSweepQCap + 1) * 64 * sizeof(uint32_t)) : kSweepScratch);
-static_assert(kSweepScratchVol == kSweepScratch, "the builds with volume moves take no more LDS per wavefront than the others");
-
-// Dynamic LDS of a walker's workgroup (byte offsets), the same arithmetic on the host (launch size) and on the device.
-// Every byte counts for the reference's own 48-molecule cells: eight walkers share a CU when a workgroup's static + dynamic
-// LDS stays within 160 KiB / 8 = 20480 B (mw_sweep_translation_launch).
-struct SweepLds { unsigned iv, pos, tab, uni, mv, scr, row, nn, mom, lmask, inmask, rec, total, scr_bytes; };
-// (a volume move's full-box energy by all wavefronts of the workgroup: two lattices entirely in LDS, four or more moves in flight)
-__host__ __device__ constexpr bool sweep_split(int L, bool ldslist, bool withvol, int spec) { return ldslist && withvol && L == 2 && spec >= 4; }
-__host__ __device__ inline SweepLds sweep_lds(int L, int nw, int ivcap, int N, int nbins, bool ldspos, bool ldslist, int rstride, bool withvol,
-                                              bool samplerun, int spec = 1)
-{
-    SweepLds o;
-    unsigned p = 0;
-    o.iv = p;  p += (unsigned)L * ivcap * 24u;                         // image vectors [L][ivcap][3]
-    o.pos = p; p += ldspos ? (unsigned)L * N * 24u : 0u;               // positions     [L][N][3]     (small systems)
-    o.tab = p; p += L == 2 ? (samplerun ? 5u : 4u) * nbins * 8u : 0u;  // weight, mu_bin, binwidth, histogram; unbiased_hist in a sample run only
-    o.uni = p; p += (unsigned)sweep_batch(withvol, spec) * 8u * 8u;    // uniforms of a batch of moves [kUB][8]
-    o.mv = o.uni;                                                      // a translation's molecule + displacement {x, y, z, imol}: written over its
-                                                                       // spent uniforms u0..u3 (a volume move keeps its own: it reads them again)
-    p = (p + 15u) & ~15u;
-    o.scr_bytes = withvol ? kSweepScratchVol : kSweepScratch;          // per wavefront: WaveScratch / the full-box energy's queue
-    o.scr = p; p += (unsigned)nw * o.scr_bytes;
-    o.row = p; p += ldslist ? (unsigned)L * N * rstride * 2u : 0u;     // list rows, 16-bit entries (j | image << 6; N <= 64)
-    o.nn = p;  p += ldslist ? (unsigned)L * N : 0u;                    // row lengths, one byte each
-    p = (p + 15u) & ~15u;
-    // look-ahead builds (a handful of walkers: LDS to spare) keep the moment path's data here: every molecule's moments, current and
-    // a volume move's trial set [2][L][N][kMomStride], and every row's molecules as a bit mask [L][N]
-    const bool momlds = ldslist && spec > 1;
-    o.mom = p;   p += momlds ? 2u * L * N * (unsigned)kMomStride * 8u : 0u;
-    o.lmask = p; p += momlds ? (unsigned)L * N * 8u : 0u;
-    const bool split = sweep_split(L, ldslist, withvol, spec);
-    o.inmask = p; p += split ? (unsigned)L * N * 4u : 0u;
-    p = (p + 15u) & ~15u;
-    o.rec = p;    p += split ? (unsigned)L * N * 12u * 48u : 0u;              // [L][N][kSplitQ][6] doubles
-    o.total = (p + 15u) & ~15u;
-    return o;
-}
-
-// SPLIT: a volume move's full-box energy (compute_model_energy, molint.F90:407-499) spread over ALL wavefronts of a look-ahead
-// workgroup -- the builds of a handful of walkers, whose wavefronts beyond one per lattice have nothing else to do during a volume
-// move, and whose speed is one chain's: the one-wavefront routine above walks a molecule's row and its ~8 in-range neighbours' pair
-// terms (rsqrt, reciprocal, exp) one after the other, 7 of a volume move's 16 us.  Walkers entirely in LDS, lane = molecule,
-// wavefront `part` of `nparts` of the lattice:
-//   A  distance tests of row slots part, part + nparts, ...: the in-range slots are OR-ed into inmask[molecule];
-//   B  in-range neighbour q (in list order) of every molecule by wavefront q mod nparts: {d, 1/r, e1, g} into rec[molecule][q];
-//   C  the lattice's first wavefront adds the records up in list order with atom_energy's own arithmetic (MomentSums): the energy
-//      and the moments are atom_energy's bit for bit, so the chain does not depend on the look-ahead of the build that runs it.
-// Between the phases: the caller's workgroup barriers.  B reports a molecule with more than kSplitQ in-range neighbours (`overflow`):
-// the caller then takes the one-wavefront routine.
-__device__ __forceinline__ void dev_split_tests(const VolCtx& c, int l, int part, int nparts, int lane)
-{
-    const int mol = lane < c.N ? lane : 0;
-    const bool act = lane < c.N;
-    const double* Ps = c.spos + (size_t)l * c.N * 3;
-    const double* IVl = c.siv + (size_t)l * c.ivcap * 3;
-    const int n = act ? (int)c.snn[l * c.N + mol] : 0;
-    const int nmax = __builtin_amdgcn_readfirstlane(wave_max_i(n));
-    const unsigned short* row = c.srow + ((size_t)l * c.N + mol) * c.rstride;
-    const double xi = Ps[3 * mol], yi = Ps[3 * mol + 1], zi = Ps[3 * mol + 2];
-    unsigned m = 0u;
-    for (int s = part; s < nmax; s += nparts) {
-        const uint32_t e = s < n ? (uint32_t)row[s] : 0u;
-        const double* pj = Ps + 3 * (size_t)(e & 63u);
-        const double* iv = IVl + 3 * (size_t)(e >> 6);
-        const double dx = (pj[0] + iv[0]) - xi, dy = (pj[1] + iv[1]) - yi, dz = (pj[2] + iv[2]) - zi;     // molint.F90:447,450
-        const double r2 = dist2(dx, dy, dz);
-        if (s < n && r2 < kRcSq) m |= 1u << s;                                                          // :454
-    }
-    if (m != 0u) atomicOr(&c.inmask[l * c.N + mol], m);
-}
-
-__device__ __forceinline__ bool dev_split_records(const VolCtx& c, int l, int part, int nparts, int lane)
-{
-    const int mol = lane < c.N ? lane : 0;
-    const bool act = lane < c.N;
-    const double* Ps = c.spos + (size_t)l * c.N * 3;
-    const double* IVl = c.siv + (size_t)l * c.ivcap * 3;
-    const unsigned short* row = c.srow + ((size_t)l * c.N + mol) * c.rstride;
-    const double xi = Ps[3 * mol], yi = Ps[3 * mol + 1], zi = Ps[3 * mol + 2];
-    const unsigned mask = act ? c.inmask[l * c.N + mol] : 0u;
-    const int cnt = __popc(mask);
-    double* R = c.rec + ((size_t)l * c.N + mol) * kSplitQ * 6;
-    for (int q = part; q < kSplitQ; q += nparts) {            // (uniform bounds; a lane with fewer in-range neighbours sits the step out)
-        if (q < cnt) {
-            unsigned mm = mask;
-            for (int t = 0; t < q; ++t) mm &= mm - 1u;        // the q-th in-range slot
-            const int s = __ffs((int)mm) - 1;
-            const uint32_t e = (uint32_t)row[s];
-            const double* pj = Ps + 3 * (size_t)(e & 63u);
-            const double* iv = IVl + 3 * (size_t)(e >> 6);
-            const double dx = (pj[0] + iv[0]) - xi, dy = (pj[1] + iv[1]) - yi, dz = (pj[2] + iv[2]) - zi;
-            const double r2 = dist2(dx, dy, dz);
-            double rinv, e1, g;
-            pair_terms(r2, rinv, e1, g);                                                  // :456-462
-            double2* r2p = reinterpret_cast<double2*>(R + 6 * q);
-            r2p[0] = make_double2(dx, dy); r2p[1] = make_double2(dz, rinv); r2p[2] = make_double2(e1, g);
-        }
-    }
-    return __ballot(cnt > kSplitQ) != 0ull;
-}
-
-// (value in every lane, like dev_wave_model_energy)
-__device__ __forceinline__ double dev_split_sum(const VolCtx& c, int l, int lane, double* __restrict__ mom_l, double* lane_e = nullptr)
-{
-    const int mol = lane < c.N ? lane : 0;
-    const bool act = lane < c.N;
-    const int cnt = act ? __popc(c.inmask[l * c.N + mol]) : 0;
-    const double* R = c.rec + ((size_t)l * c.N + mol) * kSplitQ * 6;
-    MomentSums ms;
-    for (int q = 0; q < cnt; ++q) {
-        const double2* r2p = reinterpret_cast<const double2*>(R + 6 * q);
-        const double2 a = r2p[0], b = r2p[1], d = r2p[2];
-        ms.add(a.x, a.y, b.x, b.y, d.x, d.y);
-    }
-    double esum = 0.0;
-    const double e = ms.finish(cnt, (mom_l && act) ? mom_l + (size_t)mol * kMomStride : nullptr);
-    if (lane_e) *lane_e = e;
-    if (act) esum += e;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) esum += __shfl_xor(esum, off, 64);
-    return esum;
-}
-
-// Volume move of one walker (mc_volume, mc_moves.F90:1216-1534; ref_ljr, which only chain synchronisation reads, is not
-// carried).  Rare (probability ~1/N per move).  One symmetric hmatrix element of both lattices changes; every wavefront
-// rescales ITS lattice through fractional coordinates (lanes over molecules), rebuilds its image vectors in the
-// reference's order and arithmetic and recomputes its full-box energy WITH THE EXISTING LISTS (atom_energy over the
-// slot-major list); wavefront 0 decides; on rejection every wavefront puts its lattice back the way the reference does
-// (positions mapped back through the NEW reciprocal matrix, :1413-1506).
-// Returns (every wavefront): 1 accepted, 0 rejected, -1 rejected because a cell needed more image vectors than ivcap.
-// With look-ahead (NW > NLAT wavefronts) the wavefronts beyond the first NLAT have no lattice of their own here: they keep
-// the workgroup's barriers company.
-template <int NLAT, int NW, bool LDSPOS, bool SPLIT, typename DecideFn>
-__device__ __forceinline__
-int volume_move_wg(const VolCtx& c, const double* __restrict__ U, double dv_max, int wv, int lane,
-                   double* __restrict__ sx, int* __restrict__ sdec, DecideFn decide)
-{
-    constexpr int L = NLAT;
-    const bool active = wv < NLAT;
-    const int l = active ? wv : 0;                                                 // this wavefront's lattice
-    [[maybe_unused]] const unsigned long long tv0 = MW_SW_NOW();
-    // the old cell of this lattice, kept in LDS (c.sbk: [lattice][hmatrix 9 | recip 9 | new recip 9]): eighteen wave-uniform
-    // doubles are thirty-six vector registers, held across the full-box energy evaluation
-    double* bk_h = c.sbk + 27 * l;
-    double* bk_r = bk_h + 9;
-    double* bk_n = bk_h + 18;
-    if (active && lane < 9) { bk_h[lane] = c.shmat[l * 9 + lane]; bk_r[lane] = c.srecip[l * 9 + lane]; }
-    const double old_vol_l = c.svol[l];
-    const int idim = (int)(U[0] * 3.0) + 1, jdim = (int)(U[1] * 3.0) + 1;                       // :1269-1272
-    const double dh = (2.0 * U[2] - 1.0) * dv_max;                                              // :1276
-    wg_sync<NW>();                                     // (everybody has read the old cells)
-    if (active && lane == 0) {                                                                  // :1281-1282
-        MW_HM(c.shmat + 9 * l, idim, jdim) = MW_HM(c.shmat + 9 * l, idim, jdim) + dh;
-        if (idim != jdim) MW_HM(c.shmat + 9 * l, jdim, idim) = MW_HM(c.shmat + 9 * l, jdim, idim) + dh;
-    }
-    wg_sync<NW>();
-    // The reference takes the lattices in turn and stops at the first whose new cell needs more image vectors than there
-    // is room for (:1285-1358; here: the move counts as rejected and is flagged): lattice 2 is then never touched.
-    bool bad0 = false;
-    if (L == 2 && l == 1) {
-        const double* h = c.shmat;
-        const double rc = kSmallA * kSigma;
-        const int im = (int)floor(rc / sqrt(h[0] * h[0] + h[1] * h[1] + h[2] * h[2])) + 1;
-        const int jm = (int)floor(rc / sqrt(h[3] * h[3] + h[4] * h[4] + h[5] * h[5])) + 1;
-        const int km = (int)floor(rc / sqrt(h[6] * h[6] + h[7] * h[7] + h[8] * h[8])) + 1;
-        bad0 = (2 * im + 1) * (2 * jm + 1) * (2 * km + 1) > c.ivcap;
-    }
-    double new_e = 0.0;
-    int bad = 0;
-    bool rescaled = false;
-    [[maybe_unused]] const unsigned long long tv1 = MW_SW_NOW();
-    MW_SW_ACC(34, tv1 - tv0);
-    if (active && !bad0) {
-        dev_rescale<LDSPOS>(c, l, bk_r, c.shmat + 9 * l, lane);
-        rescaled = true;
-        wave_sync();
-        MW_SW_ACC(35, MW_SW_NOW() - tv1);
-        const int niv = dev_compute_ivects(c.shmat + 9 * l, c.siv + (size_t)l * c.ivcap * 3,
-                                           c.ivect_g + (size_t)l * c.ivcap * 3, c.ivcap, lane);
-        if (lane == 0) {
-            c.svol[l] = fabs(dev_det3(c.shmat + 9 * l));
-            double rcp[9];
-            dev_recipmatrix(c.shmat + 9 * l, rcp);
-#pragma unroll
-            for (int t = 0; t < 9; ++t) c.srecip[l * 9 + t] = rcp[t];
-            if (niv >= 0) { c.sniv[l] = niv; c.nivect_g[l] = niv; }
-        }
-        wave_sync();
-        [[maybe_unused]] const unsigned long long tv2 = MW_SW_NOW();
-        if (niv < 0) bad = 1;
-        else if constexpr (!SPLIT) new_e = dev_wave_model_energy<LDSPOS, (NW > NLAT)>(c, l, lane, c.mom_trial ? c.mom_trial + (size_t)l * c.N * kMomStride : nullptr);
-        MW_SW_ACC(36, MW_SW_NOW() - tv2); MW_SW_ACC(37, tv2 - tv1);
-    }
-    if constexpr (SPLIT) {
-        // the full-box energy by every wavefront of the workgroup (see dev_split_tests): sdec[2 + lattice] != 0 -- a cell that is
-        // not to be evaluated (bad, or lattice 2 after a bad lattice 1); sdec[0] -- a molecule with more in-range neighbours than
-        // the records hold
-        [[maybe_unused]] const unsigned long long tv2 = MW_SW_NOW();
-        constexpr int P = NW / NLAT;
-        const int lw = wv % NLAT, part = wv / NLAT;
-        if (active && lane == 0) sdec[2 + l] = bad | (bad0 ? 2 : 0);
-        if (part == 1 && lane < c.N) c.inmask[lw * c.N + lane] = 0u;                 // (a wavefront that is idle until here)
-        if (wv == NLAT && lane == 0) sdec[0] = 0;
-        wg_sync<NW>();                                  // the trial cell -- positions, image vectors -- is there for everybody
-        const bool run = sdec[2 + lw] == 0;
-        if (run) dev_split_tests(c, lw, part, P, lane);
-        wg_sync<NW>();
-        if (run && dev_split_records(c, lw, part, P, lane) && lane == 0) sdec[0] = 1;
-        wg_sync<NW>();
-        if (active && !bad0 && !bad) {
-            double* mom_l = c.mom_trial ? c.mom_trial + (size_t)l * c.N * kMomStride : nullptr;
-            new_e = sdec[0] != 0 ? dev_wave_model_energy<LDSPOS, true>(c, l, lane, mom_l) : dev_split_sum(c, l, lane, mom_l);
-#ifdef MW_SPLIT_CHECK     // diagnostic build (tools/variants.py splitcheck): the split sum against the one-wavefront routine, molecule by molecule
-                          // -- g_sweep_stamps[44] lattice energies checked, [45] of them with a molecule that differs, [43], [46], [47] the last such
-            if (sdec[0] == 0) {
-                double es = 0.0;
-                (void)dev_split_sum(c, l, lane, nullptr, &es);
-                const int mol = lane < c.N ? lane : 0;
-                const int n = lane < c.N ? (int)c.snn[l * c.N + mol] : 0;
-                const int nmax = __builtin_amdgcn_readfirstlane(wave_max_i(n));
-                const unsigned short* row = c.srow + ((size_t)l * c.N + mol) * c.rstride;
-                const double* Ps = c.spos + (size_t)l * c.N * 3;
-                const double* IVl = c.siv + (size_t)l * c.ivcap * 3;
-                auto getiv = [&](int k, double& x, double& y, double& z) { x = IVl[3 * k]; y = IVl[3 * k + 1]; z = IVl[3 * k + 2]; };
-                auto getpos = [&](int j, double& x, double& y, double& z) { const double* p = Ps + 3 * (size_t)j; x = p[0]; y = p[1]; z = p[2]; };
-                auto ent = [&](int s) -> uint32_t { const uint32_t e = s < n ? (uint32_t)row[s] : 0u; return (e & 63u) | ((e >> 6) << kJBits); };
-                uint32_t cur[8];
-                AtomSum a = atom_energy<64, true, true, kSweepQCap>(ListRsrc(), kNoColumn, kNoColumn, mol, n, nmax, 0, c.N, c.S, c.queue, getpos, getiv, cur, nullptr, ent);
-                const bool bad_l = lane < c.N && a.e != es;
-                const unsigned long long bm = __ballot(bad_l);
-                if (blockIdx.x == 0 && lane == 0) atomicAdd(&g_sweep_stamps[44], 1ull);
-                if (bm != 0ull && blockIdx.x == 0 && lane == __ffsll((long long)bm) - 1) {
-                    atomicAdd(&g_sweep_stamps[45], 1ull);
-                    g_sweep_stamps[43] = (unsigned long long)(a.cnt | (__popc(c.inmask[l * c.N + mol]) << 8) | (lane << 16) | (n << 24));
-                    g_sweep_stamps[46] = (unsigned long long)__double_as_longlong(a.e); g_sweep_stamps[47] = (unsigned long long)__double_as_longlong(es);
-                }
-            }
-#endif
-        }
-        MW_SW_ACC(36, MW_SW_NOW() - tv2);
-    }
-    [[maybe_unused]] const unsigned long long tv3 = MW_SW_NOW();
-    if (active && lane == 0) { sx[l] = new_e; sdec[2 + l] = bad; }
-    wg_sync<NW>();
-    int ok = 0, anybad = 0;
-    if (wv == 0) {
-        anybad = sdec[2] | (L == 2 ? sdec[3] : 0);
-        ok = decide(sx[0], L == 2 ? sx[1] : 0.0, anybad);          // (updates the walker's state; energies in every lane)
-        if (lane == 0) { sdec[0] = ok; sdec[1] = anybad; }
-    }
-    wg_sync<NW>();
-    [[maybe_unused]] const unsigned long long tv4 = MW_SW_NOW();
-    MW_SW_ACC(38, tv4 - tv3);
-    ok = sdec[0]; anybad = sdec[1];
-    if (active && !ok) {                                                                         // :1426-1530
-        if (lane < 9) bk_n[lane] = c.srecip[l * 9 + lane];
-        wave_sync();
-        if (lane < 9) { c.shmat[l * 9 + lane] = bk_h[lane]; c.srecip[l * 9 + lane] = bk_r[lane]; }
-        if (lane == 0) c.svol[l] = old_vol_l;
-        wave_sync();
-        if (rescaled) {
-            dev_rescale<LDSPOS>(c, l, bk_n, c.shmat + 9 * l, lane);                                      // back through the NEW recip
-            const int niv = dev_compute_ivects(c.shmat + 9 * l, c.siv + (size_t)l * c.ivcap * 3,
-                                               c.ivect_g + (size_t)l * c.ivcap * 3, c.ivcap, lane);   // :1510-1512
-            if (lane == 0 && niv > 0) { c.sniv[l] = niv; c.nivect_g[l] = niv; }
-        }
-    }
-    if (active && lane == 0) {                         // global mirrors of the cell
-#pragma unroll
-        for (int t = 0; t < 9; ++t) c.hmat_g[l * 9 + t] = c.shmat[l * 9 + t];
-        c.vol_g[l] = c.svol[l];
-    }
-    wg_sync<NW>();
-    MW_SW_ACC(39, MW_SW_NOW() - tv4); MW_SW_ACC(40, 1ull); MW_SW_ACC(41, MW_SW_NOW() - tv0);
-    return anybad ? -1 : ok;
-}
 
 // =====================================================================================
 // k_sweep: the device-resident Monte Carlo driver.  grid = walkers of the launch, block = 64 x NLAT.
@@ -621,38 +26,6 @@ int volume_move_wg(const VolCtx& c, const double* __restrict__ U, double dv_max,
 //    not in registers: a wave-uniform double costs two VECTOR registers, and thirty of them held across the energy
 //    evaluation were the difference between two and four wavefronts per SIMD.
 // =====================================================================================
-struct WalkerCtl {
-    // the launch's parameters as this walker sees them (its own window, step sizes, increment)
-    double beta, pressure, dref, av_binwidth, log_unbiased_norm, transP, ref1, ref2, wl_alpha, orig_wl_factor, mu_min, mu_max;
-    double max_trans, dv_max;
-    MuGridDev mg;                            // (mg.in_window changes at the top of a 'dd' cycle)
-    int record, samplerun, always_switch, npt, swetnam, dd, minu, eq_cycles, nbins;
-    int tab_small;                           // every |weight| < 2^20 (the lattice switch's shortcut; kept up with every update)
-    // the walker's state between moves
-    double men0, men1, ls_mu, gauge, wlf, sumh, cur_min, lgv12, lgv21;
-    unsigned long long acc, nsw, nvol_try, nvol_acc;
-    int ls, k_cur, k_valid, flag, cyc, within;
-};
-
-// The MINU branch of both move types: the lattice the move would end in; diffkT rewritten with the switch's terms if it differs.
-// E = trial energies, V = trial volumes, Eb / Vb = energy and volume of the CURRENT lattice before the move.
-__device__ __forceinline__ int dev_minu_branch(const WalkerCtl& sp, int ls, double E1, double E2, double V1, double V2,
-                                               double Eb, double Vb, bool vol_terms, int N, double new_eta, double old_eta,
-                                               double& diffkT)
-{
-    const double h1 = E1 + sp.pressure * V1 - sp.ref1, h2 = E2 + sp.pressure * V2 - sp.ref2;   // minloc, :1122-1126
-    const int lsn = h2 < h1 ? 2 : 1;
-    if (lsn != ls) {
-        const double En = lsn == 1 ? E1 : E2, Vn = lsn == 1 ? V1 : V2;
-        double d;
-        if (vol_terms) d = sp.beta * En - sp.beta * Eb + sp.beta * sp.pressure * (Vn - Vb) - (double)N * fast_log_pos(Vn / Vb) + new_eta - old_eta;   // :1131-1133,1396-1397
-        else           d = sp.beta * En - sp.beta * Eb + new_eta - old_eta;                                                                  // :1135
-        if (sp.ref1 != 0.0 || sp.ref2 != 0.0)                                                                                               // leshift, :1134,1136,1398
-            d = d - sp.beta * (lsn == 1 ? sp.ref1 : sp.ref2) + sp.beta * (ls == 1 ? sp.ref1 : sp.ref2);
-        diffkT = d;
-    }
-    return lsn;
-}
 
 // SPEC > 1: LOOK-AHEAD for walkers that cannot fill the chip by their number (a few thousand 4096-molecule boxes leave two
 // wavefronts per SIMD; a few dozen leave almost all of it idle).  The workgroup holds SPEC wavefronts per lattice and
@@ -714,7 +87,6 @@ void k_sweep(double* pos, double* hmat, double* ivect,
     double* sbw = smub + nbins;
     double* shist = sbw + nbins;
     double* suhist = shist + nbins;                       // (there in a sample run only)
-    constexpr int MVS = 8;                                // doubles between two moves' {x, y, z, imol} (sweep_lds)
     double* suni = reinterpret_cast<double*>(smem_raw + lay.uni);
     double* smv = reinterpret_cast<double*>(smem_raw + lay.mv);
     WaveScratch* ws = reinterpret_cast<WaveScratch*>(smem_raw + lay.scr + (unsigned)wv * lay.scr_bytes);
@@ -726,6 +98,8 @@ void k_sweep(double* pos, double* hmat, double* ivect,
     constexpr bool SPLIT = sweep_split(NLAT, LDSLIST, WITHVOL, SPEC);
     static_assert(kSplitQ == 12, "sweep_lds sizes the records for twelve per molecule");
     const double invPi = 1.0 / 3.141592653589793238462643383279502884197;
+    SweepView v;                                          // what the routines of mw_sweep_decide.hip.h see of all this
+    v.ctl = &ctl; v.svol = svol; v.sweight = sweight; v.smub = smub; v.sbw = sbw; v.N = N; v.lane = lane;
 
     // ---- staging: image vectors, (small systems) positions, list rows and row lengths, the walker's tables -------------
     for (int l = 0; l < L; ++l) {
@@ -821,25 +195,6 @@ void k_sweep(double* pos, double* hmat, double* ivect,
     }
     __syncthreads();
 
-
-    // mc_lattice_switch's exponent for a walker in lattice lsx with energies E0, E1 (:1557-1572) in two parts: the energy /
-    // volume terms that stand BEFORE "+ new_eta - old_eta" in the reference's expression, and the leshift terms added after it
-    auto switch_dk_terms = [&](double E0, double E1, int lsx, double& lesh) {
-        const double Els = lsx == 1 ? E0 : E1, Elsn = lsx == 1 ? E1 : E0;
-        const double V1 = svol[0], V2 = svol[1];
-        const double Vls = lsx == 1 ? V1 : V2, Vlsn = lsx == 1 ? V2 : V1;
-        double dk;
-        if (C.npt) dk = C.beta * Elsn - C.beta * Els + C.beta * C.pressure * (Vlsn - Vls) - (double)N * (lsx == 1 ? C.lgv21 : C.lgv12);
-        else       dk = C.beta * Elsn - C.beta * Els;
-        lesh = lsx == 1 ? C.beta * C.dref : -(C.beta * C.dref);               // leshift: - beta ref(lsn) + beta ref(ls), :1567,1572
-        return dk;
-    };
-    // ... and the whole of it less new_eta - old_eta (= eta_weight(ls_mu) - eta_weight(ls_mu): see post_move)
-    auto switch_dk = [&](double E0, double E1, int lsx) {
-        double lesh;
-        const double dk = switch_dk_terms(E0, E1, lsx, lesh);
-        return dk + lesh;
-    };
     // What follows EITHER move type (wavefront 0): mc_update_wl_bins (:1597-1689) on the walker's tables, then one
     // mc_lattice_switch attempt (:1536-1594).  eta_fin = eta_weight(ls_mu) with the weights as the move found them,
     // cmp_sw = exp(-dk) of the switch without its eta terms, ufac = exp(eta_fin - log_unbiased_norm); C.k_cur = bin of ls_mu.
@@ -946,7 +301,7 @@ void k_sweep(double* pos, double* hmat, double* ivect,
             }
             if (!plain) {
                 double lesh;
-                double d = switch_dk_terms(C.men0, C.men1, C.ls, lesh);
+                double d = switch_dk_terms(v, C.men0, C.men1, C.ls, lesh);
                 d = d + ew;
                 d = d - ew;
                 d = d + lesh;
@@ -966,7 +321,6 @@ void k_sweep(double* pos, double* hmat, double* ivect,
         MW_SW_ACC(14, MW_SW_NOW() - sw_p1);
         return sw;
     };
-
     int ls = C.ls;                               // the active lattice, followed by every wavefront
     [[maybe_unused]] const unsigned long long sw_k0 = MW_SW_NOW();
 #ifdef MW_SWEEP_STAMPS
@@ -1000,11 +354,6 @@ void k_sweep(double* pos, double* hmat, double* ivect,
     // the reference's  (mu - mu_bin) * (2 (w(hi) - w(lo)) / (bw + bw))  with the division taken out of the serial step (1e-16 relative).
     // Floating-point contraction is OFF in here: a product that the run adds to a weight in one place and the serial step in another
     // must round the same way wherever it is inlined (look-ahead = the sequential chain, bit for bit).
-    auto wave_fence = [&]() {                    // orders this wavefront's own LDS traffic for the compiler; LDS serves a wavefront in order
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
     __shared__ int bx_k[SPEC + 1];                // the run's exchange: bin, weight increment, histogram increment of every move's rejection
     __shared__ double bx_inc[SPEC + 1], bx_vis[SPEC + 1], bx_dump[2];
 #ifdef MW_RUN_SPEC1        // A/B only: the straight-line pass of the look-ahead builds also for one move at a time
@@ -1108,7 +457,7 @@ void k_sweep(double* pos, double* hmat, double* ivect,
 #else
                 if (always_switch) {                                              // mc_lattice_switch's exponential after an accepted / a rejected move
 #endif
-                    const double dk = newl ? switch_dk(mn0l, mn1l, ls_c) : switch_dk(bk0, bk1, ls_c);
+                    const double dk = newl ? switch_dk(v, mn0l, mn1l, ls_c) : switch_dk(v, bk0, bk1, ls_c);
                     // (one move at a time: every move takes the serial step, whose own exponential stream has lanes to spare -- the
                     //  argument waits there; with look-ahead the serial step is the exception and the exponential is taken here)
                     exs = !kRunPass ? -dk : exp_any(-dk);
@@ -1269,7 +618,7 @@ void k_sweep(double* pos, double* hmat, double* ivect,
                     const double mn0 = readlane_f64(mn0l, ln), mn1 = readlane_f64(mn1l, ln);
                     minu_ls = dev_minu_branch(C, ls_c, mn0, mn1, svol[0], svol[1], ls_c == 1 ? bk0 : bk1, ls_c == 1 ? svol[0] : svol[1],
                                               C.npt != 0, N, eta_new, eta_old, diffkT);
-                    if (minu_ls != ls_c && always_switch) cmpA_minu = exp_any(-switch_dk(mn0, mn1, minu_ls));
+                    if (minu_ls != ls_c && always_switch) cmpA_minu = exp_any(-switch_dk(v, mn0, mn1, minu_ls));
                 }
                 // lane 0: the acceptance; lanes 61, 62: the unbiased histogram's factor after an accepted / a rejected move (:1627-1629);
                 // one move at a time: lanes 1, 2 the lattice switch's exponentials, whose arguments the pre-phase left there
@@ -1405,7 +754,7 @@ void k_sweep(double* pos, double* hmat, double* ivect,
                     if (!plain) {
                         if (!(samplerun || !record)) ew = lane_eta(C.mg, sweight, smub, sbw, mu_c, k_c);
                         double lesh;
-                        double d = switch_dk_terms(bk0, bk1, ls_c, lesh);
+                        double d = switch_dk_terms(v, bk0, bk1, ls_c, lesh);
                         d = d + ew;
                         d = d - ew;
                         d = d + lesh;
@@ -1449,7 +798,6 @@ void k_sweep(double* pos, double* hmat, double* ivect,
         }
         wave_fence();
     };
-
     // THE MOMENT PATH of a translation (walkers entirely in LDS; move_energy_mom_wave): the i--j--k sums come from every molecule's
     // moments, kept in `wmom` (global memory, L2-resident: the walker's LDS is counted in bytes) -- made by the lattice's first
     // wavefront when sdec[2 + lattice] says so (the launch's start; an accepted move whose evaluation took another routine),
@@ -1564,52 +912,7 @@ void k_sweep(double* pos, double* hmat, double* ivect,
                     do_switch = L == 2 && C.always_switch && !(C.dd && C.cyc < C.eq_cycles);
                 }
                 if (tid < L) svold[tid] = svol[tid];               // (volume_move_wg's first barrier orders this against the decision)
-                auto decide = [&](double e0n, double e1n, int anybad) -> int {
-                    const double Vo0 = svold[0], Vo1 = L == 2 ? svold[1] : 0.0;
-                    // wavefront 0: mc_volume's acceptance (:1361-1410) and, on rejection, the restored order parameter (:1514-1530)
-                    const double bk0 = C.men0, bk1 = C.men1;
-                    const int ls0 = C.ls;
-                    double ls_mu = C.ls_mu;
-                    int okv = 0, lsn = ls0;
-                    if (!anybad) {
-                        const double Vn0 = svol[0], Vn1 = L == 2 ? svol[1] : 0.0;
-                        const double dE = (ls0 == 1 ? e0n - bk0 : e1n - bk1);                                // :1361
-                        const double Vls = ls0 == 1 ? Vn0 : Vn1, Vold = ls0 == 1 ? Vo0 : Vo1;
-                        double old_eta = 0.0, new_eta = 0.0;
-                        if (L == 2) {                                                                        // :1363-1371
-                            double mu = (e0n + C.pressure * Vn0) - (e1n + C.pressure * Vn1);
-                            mu = mu - C.dref;                                                                // :1371 (leshift)
-                            mu = mu * C.beta - (double)N * fast_log_pos(Vn0 / Vn1);
-                            const double mul = lane == 0 ? ls_mu : mu;
-                            const double el = lane_eta(C.mg, sweight, smub, sbw, mul, lane_mu_to_bin(C.mg, mul));
-                            old_eta = readlane_f64(el, 0); new_eta = readlane_f64(el, 1);
-                            ls_mu = mu;
-                        }
-                        diffkT = C.beta * dE + new_eta - old_eta + C.beta * C.pressure * (Vls - Vold)
-                                 - (double)N * fast_log_pos(Vls / Vold);                                     // :1381-1382
-                        int minu_ls = ls0;
-                        if (C.minu && L == 2)                                                                // :1385-1401
-                            minu_ls = dev_minu_branch(C, ls0, e0n, e1n, Vn0, Vn1, ls0 == 1 ? bk0 : bk1, Vold, true, N,
-                                                      new_eta, old_eta, diffkT);
-                        double cmp = exp_any(-diffkT);
-                        cmp = cmp > 1.0 ? 1.0 : cmp;
-                        okv = U[3] < cmp ? 1 : 0;                                                            // :1410
-                        if (okv) lsn = minu_ls;                                                              // :1426-1429
-                    }
-                    double m0 = e0n, m1 = e1n;
-                    if (!okv) {
-                        m0 = bk0; m1 = bk1;                                                                  // :1514
-                        if (L == 2) {                                                                        // :1516-1520 (the OLD cells)
-                            double mu = (m0 + C.pressure * Vo0) - (m1 + C.pressure * Vo1);
-                            mu = mu - C.dref;                                                                // :1526 (leshift)
-                            mu = mu * C.beta - (double)N * fast_log_pos(Vo0 / Vo1);
-                            ls_mu = mu;
-                        }
-                    }
-                    if (lane == 0) { C.men0 = m0; C.men1 = m1; C.ls_mu = ls_mu; C.ls = lsn; }
-                    wave_sync();
-                    return okv;
-                };
+                auto decide = [&](double e0n, double e1n, int anybad) -> int { return decide_volume<NLAT>(v, svold, U, diffkT, e0n, e1n, anybad); };
                 const int rv = volume_move_wg<NLAT, NW, LDSPOS, SPLIT>(vc, U, C.dv_max, wv, lv, sx, sdec, decide);
                 if (usemom && rv == 1) msel ^= 1;                  // (the trial cell's moments are the walker's now)
                 if (wv == 0) {
@@ -1629,7 +932,7 @@ void k_sweep(double* pos, double* hmat, double* ivect,
                         if (lane == 0) { C.k_cur = kl; C.k_valid = 1; }
                         wave_sync();
                         const double eta_fin = readlane_f64(lane_eta(C.mg, sweight, smub, sbw, mu, kl), 0);
-                        const double dk = do_switch ? switch_dk(C.men0, C.men1, C.ls) : 0.0;
+                        const double dk = do_switch ? switch_dk(v, C.men0, C.men1, C.ls) : 0.0;
                         const double ex = exp_any(lane == 0 ? -dk : eta_fin - C.log_unbiased_norm);
                         sw = post_move(eta_fin, readlane_f64(ex, 0), readlane_f64(ex, 1), do_switch, U[6]);
                     }

@@ -42,13 +42,13 @@ def test_sweep_kernels_keep_their_register_budget(tmp_path):
     from mc_water_ls_mw_amd import build as mwbuild
     mwbuild.build()
     notes = subprocess.run([READELF, "--notes", _gfx950_code_object(tmp_path)], capture_output=True, text=True, check=True).stdout
-    seen = 0
+    seen = []
     for blk in notes.split("- .agpr_count")[1:]:
         name = re.search(r"\.name:\s+(\S+)", blk).group(1)
         m = re.match(r"_ZN2mw7k_sweepILi([12])ELi([12468])ELb([01])ELb([01])ELb([01])E", name)
         if not m:
             continue
-        seen += 1
+        seen.append(tuple(int(x) for x in m.groups()))
         get = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1))     # noqa: E731
         three = m.group(1) == "2" and m.group(2) != "1"                           # two lattices + look-ahead
         # (the builds that also carry mc_volume AND the moment path of the walkers in LDS -- scalar registers run out first there and
@@ -56,8 +56,12 @@ def test_sweep_kernels_keep_their_register_budget(tmp_path):
         withvol_lds = m.group(5) == "1" and m.group(4) == "1"
         assert get("vgpr_spill_count") <= (16 if withvol_lds else 8), (name, get("vgpr_spill_count"))
         assert get("vgpr_count") <= (168 if three else 128), (name, get("vgpr_count"))
-    assert seen == 40          # lattices x residency x with / without volume moves, + look-ahead 2 / 4 for walkers in global memory
-                               # and for walkers entirely or partly in LDS, + 8 for one-lattice walkers in global memory
+    # (lattices, look-ahead, positions in LDS, rows in LDS, volume moves): lattices x residency x with / without volume moves, for one
+    # move at a time and look-ahead 2 / 4; 8 only for one-lattice walkers in global memory, 6 only for two lattices entirely in LDS
+    residencies = ((0, 0), (1, 0), (1, 1))
+    want = {(nlat, ahead, p, r, vol) for nlat in (1, 2) for ahead in (1, 2, 4) for p, r in residencies for vol in (0, 1)}
+    want |= {(1, 8, 0, 0, vol) for vol in (0, 1)} | {(2, 6, 1, 1, vol) for vol in (0, 1)}
+    assert len(want) == 40 and len(seen) == 40 and set(seen) == want, sorted(set(seen) ^ want)
 
 
 @pytest.mark.skipif(not os.path.exists(READELF), reason="llvm-readelf not in this image")
