@@ -171,7 +171,7 @@ __device__ __forceinline__ void pair_terms(double r2, double& rinv, double& e1, 
 //   vectors)   [9] the number of in-range neighbours
 // -- what the i--j--k triplet sum of a molecule i next to j needs of j's other neighbours:
 //   sum_k g_k (u_i . u_k - c0)^2 = u_i^T S2 u_i - 2 c0 u_i . S1 + c0^2 S0.
-constexpr int kMomStride = 10;   // doubles per molecule (80 bytes: five 16-byte stores / loads -- the full-box pass that writes them is bound by those bytes)
+constexpr int kMomStride = 10;   // doubles per molecule (80 bytes: five 16-byte pieces -- the full-box pass writes them a wavefront at a time, in whole records: store_moments_wave)
 
 // ---- staged vectors in LDS ------------------------------------------------------------
 // LDS layout of the staged positions and image vectors (what a random gather costs the LDS: MI355X_MICROARCH.md,

@@ -75,8 +75,9 @@ struct MomentSums {
         Sxy = __builtin_fma(hx, dy, Sxy); Sxz = __builtin_fma(hx, dz, Sxz); Syz = __builtin_fma(hy, dz, Syz);
     }
     // the molecule's energy (:464,483); its moments to mom_out (per lane, or nullptr; 16-byte stores: a divergent store costs its 64
-    // addresses, whatever their width)
-    __device__ __forceinline__ double finish(int cnt, double* __restrict__ mom_out) const
+    // addresses, whatever their width) or, as the same five 16-byte pieces, into `rec` for a caller that stores them itself
+    // (store_moments_wave below)
+    __device__ __forceinline__ double finish(int cnt, double* __restrict__ mom_out, double2* __restrict__ rec = nullptr) const
     {
 #pragma clang fp contract(off)
         // (every multiply-add explicit: one rounding sequence wherever this is inlined)
@@ -89,6 +90,10 @@ struct MomentSums {
             double2* m2 = reinterpret_cast<double2*>(mom_out);
             m2[0] = make_double2(S0, S1x); m2[1] = make_double2(S1y, S1z); m2[2] = make_double2(Sxx, Syy);
             m2[3] = make_double2(Sxy, Sxz); m2[4] = make_double2(Syz, (double)cnt);
+        }
+        if (rec) {
+            rec[0] = make_double2(S0, S1x); rec[1] = make_double2(S1y, S1z); rec[2] = make_double2(Sxx, Syy);
+            rec[3] = make_double2(Sxy, Sxz); rec[4] = make_double2(Syz, (double)cnt);
         }
         return __builtin_fma(0.5, e2, kLamEps * T);
     }
@@ -126,7 +131,8 @@ struct ListFromGlobal { static constexpr bool kGlobal = true; __device__ uint32_
 template <int BLOCK, bool BATCH4, bool LEAN = false, int QCAP = kQCap, typename PosFn, typename IvFn, typename EntFn = ListFromGlobal>
 __device__ __forceinline__ AtomSum atom_energy(ListRsrc rs, uint32_t col, uint32_t col_next, int mol, int n, int nmax, int c0min,
                                                int N, int S, uint32_t* __restrict__ queue, PosFn getpos, IvFn getiv,
-                                               uint32_t (&cur)[8], double* __restrict__ mom_out = nullptr, EntFn ent = ListFromGlobal())
+                                               uint32_t (&cur)[8], double* __restrict__ mom_out = nullptr, EntFn ent = ListFromGlobal(),
+                                               double2* __restrict__ rec = nullptr)   // (rec: MomentSums::finish)
 {
     constexpr bool kEnt = !std::is_same<EntFn, ListFromGlobal>::value;
     static_assert(!kEnt || LEAN, "list entries from a functor: the lean variant only");
@@ -250,9 +256,61 @@ __device__ __forceinline__ AtomSum atom_energy(ListRsrc rs, uint32_t col, uint32
         }
     }
     AtomSum out;
-    out.e  = ms.finish(cnt, mom_out);
+    out.e  = ms.finish(cnt, mom_out, rec);
     out.cnt = cnt;
     return out;
+}
+
+// The moments of a wavefront's group of 64 molecules, stored in whole 80-byte runs.  Each lane arrives with its own molecule's
+// record (`rec`: five 16-byte pieces) and its molecule index (`mol`, negative: nothing to store -- the inactive lanes of a box's last
+// group).  A lane storing its own record makes every store instruction 64 unrelated 16-byte writes at the scattered addresses of
+// the sorted order; here the 320 pieces are re-dealt through LDS so that consecutive lanes hold consecutive pieces of one record:
+// store `it` (0..4) carries piece p = it*64 + lane = part p % 5 of the record of lane p / 5 -- still five store instructions, each
+// now made of thirteen 80-byte runs.  Same values at the same addresses as the per-lane stores.
+// The staging area is the wavefront's own segment of the in-range queue (`wq`: its column 0; rows of 64 words, BLOCK words apart),
+// idle between two calls of atom_energy (the prefetch of the next group's list chunk lives in registers).  Its kQCap + 1 rows hold
+// half a group's records (32 x 80 B = 10 rows) and, in row 10, the 64 molecule indices: two halves, the store that straddles them
+// (it = 2) gathered from both.  Wave-local: LDS serves a wavefront's accesses in order, the fences keep the compiler to it.
+template <int BLOCK>
+__device__ __forceinline__ void store_moments_wave(uint32_t* __restrict__ wq, const double2 (&rec)[5], int mol, double* __restrict__ M, int lane)
+{
+    static_assert(kQCap + 1 >= 11, "ten rows of records and one of molecule indices");
+    // (the staging addresses are worked out here, from a lane number the compiler cannot hoist: as invariants of the kernel's group
+    //  loop they were sixteen more registers held from group to group, in a kernel that has none to spare)
+    asm volatile("" : "+v"(lane));
+    auto piece = [&](int q) { return reinterpret_cast<double2*>(wq + (q >> 4) * BLOCK + (q & 15) * 4); };   // piece q of the staged half
+    auto sync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    auto stage = [&](int h) {
+        if ((lane >> 5) == h) {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) *piece((lane & 31) * 5 + k) = rec[k];
+        }
+        sync();
+    };
+    int* smol = reinterpret_cast<int*>(wq + 10 * BLOCK);
+    sync();                                              // (every lane is done with its queue column)
+    smol[lane] = mol;
+    auto store = [&](int it, double2 v) {                // (each store leaves as soon as its pieces are read: nothing held but v2)
+        const unsigned p = (unsigned)(it * 64 + lane), r = p / 5u, part = p - 5u * r;
+        const int m = smol[r];
+        if (m >= 0) reinterpret_cast<double2*>(M + (size_t)m * kMomStride)[part] = v;
+    };
+    stage(0);                                            // pieces 0 .. 159
+    store(0, *piece(lane));
+    store(1, *piece(64 + lane));
+    double2 v2 = make_double2(0.0, 0.0);
+    if (lane < 32) v2 = *piece(128 + lane);
+    sync();
+    stage(1);                                            // pieces 160 .. 319
+    if (lane >= 32) v2 = *piece(lane - 32);
+    store(2, v2);
+    store(3, *piece(32 + lane));
+    store(4, *piece(96 + lane));
+    sync();                                              // (the segment is the queue again)
 }
 
 constexpr int kMaxGroups = 128;          // groups of 64 list columns per workgroup (chunk <= 8192)
@@ -270,7 +328,8 @@ constexpr int kStageTicket = 64 * 12;    // doubles of the next box per staging 
 // draws staging tickets (768 doubles of the next box each) and holds them in registers -- free now that its evaluation
 // is over -- until the slowest wavefront arrives at the barrier; then the registers go to LDS.  The HBM round trip of
 // the staging overlaps the workgroup's tail instead of following it; so do the first list reads of the next box.
-// MOMOUT: the build that also leaves every molecule's moments behind (`mom`); the plain build carries none of its registers.
+// MOMOUT: the build that also leaves every molecule's moments behind (`mom`), stored a group of 64 records at a time
+// (store_moments_wave); the plain build carries none of its registers and none of its LDS traffic.
 template <bool LDSPOS, int BLOCK, int LAYOUT, bool BATCH4 = false, bool MOMOUT = false>
 __global__ __launch_bounds__(BLOCK)
 void k_model_energy(const double* __restrict__ pos, const double* __restrict__ ivect,
@@ -362,9 +421,16 @@ void k_model_energy(const double* __restrict__ pos, const double* __restrict__ i
                 if (tn < a1) { col_next = (uint32_t)tn * 4u; n_next = NNS[tn]; mol_next = ORD[tn]; }
             }
             const int cm = __builtin_amdgcn_readfirstlane(CM[grp]);
-            double* mo = (MOMOUT && act) ? mom + ((size_t)b * N + mol) * kMomStride : nullptr;
-            AtomSum a = atom_energy<BLOCK, BATCH4>(rs, col, col_next, mol, act ? (n_cur & 0xff) : 0, cm & 0xff, cm >> 8, N, S,
-                                           queue, getpos, getiv, cur, mo);
+            AtomSum a;
+            if constexpr (MOMOUT) {
+                double2 rec[5];
+                a = atom_energy<BLOCK, BATCH4>(rs, col, col_next, mol, act ? (n_cur & 0xff) : 0, cm & 0xff, cm >> 8, N, S,
+                                               queue, getpos, getiv, cur, nullptr, ListFromGlobal(), rec);
+                store_moments_wave<BLOCK>(queue - lane, rec, act ? mol : -1, mom + (size_t)b * N * kMomStride, lane);
+            } else {
+                a = atom_energy<BLOCK, BATCH4>(rs, col, col_next, mol, act ? (n_cur & 0xff) : 0, cm & 0xff, cm >> 8, N, S,
+                                               queue, getpos, getiv, cur);
+            }
             if (act) { np += (unsigned int)a.cnt; nt += (unsigned int)(a.cnt * (a.cnt - 1) / 2); }
             const double ge = dpp_wave_sum(act ? a.e : 0.0);             // fixed tree; total in lane 63
             if (lane == 63) gsum[grp - g0] = ge;
