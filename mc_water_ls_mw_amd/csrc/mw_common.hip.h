@@ -165,13 +165,19 @@ __device__ __forceinline__ void pair_terms(double r2, double& rinv, double& e1, 
 }
 
 // Per-molecule MOMENTS of the in-range neighbourhood, the by-product of the full-box pass that the single-move kernel's moment
-// path consumes (mw_move_energy.hip.h, move_energy_mom_wave): with g_k = exp(gamma sigma/(r_jk - a sigma)) and u_k the unit vector
+// path consumes (mw_move_moments.hip.h, move_energy_mom_wave): with g_k = exp(gamma sigma/(r_jk - a sigma)) and u_k the unit vector
 // from j to its in-range neighbour k,
 //   [0] S0 = sum g_k   [1..3] S1 = sum g_k u_k   [4..8] S2 = sum g_k u_k u_k^T (xx, yy, xy, xz, yz; zz = S0 - xx - yy: the u_k are unit
 //   vectors)   [9] the number of in-range neighbours
 // -- what the i--j--k triplet sum of a molecule i next to j needs of j's other neighbours:
 //   sum_k g_k (u_i . u_k - c0)^2 = u_i^T S2 u_i - 2 c0 u_i . S1 + c0^2 S0.
 constexpr int kMomStride = 10;   // doubles per molecule (80 bytes: five 16-byte pieces -- the full-box pass writes them a wavefront at a time, in whole records: store_moments_wave)
+__device__ __forceinline__ void load_moments(const double* m, double (&M)[10])      // one molecule's record, as five 16-byte loads
+{
+    const double2* m2 = reinterpret_cast<const double2*>(m);
+#pragma unroll
+    for (int c = 0; c < 5; ++c) { const double2 v = m2[c]; M[2 * c] = v.x; M[2 * c + 1] = v.y; }
+}
 
 // ---- staged vectors in LDS ------------------------------------------------------------
 // LDS layout of the staged positions and image vectors (what a random gather costs the LDS: MI355X_MICROARCH.md,
@@ -241,6 +247,13 @@ __device__ __forceinline__ void stage_iv_end(double* __restrict__ siv, const dou
 }
 
 // ---- wave / block reductions ---------------------------------------------------------
+__device__ __forceinline__ void wave_fence()     // orders this wavefront's own LDS traffic for the compiler; LDS serves a wavefront in order
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // Inclusive prefix sums over the 64 lanes through the DPP network: four shifts inside each row of 16
 // lanes, then lane 15 of a row into the next row and lane 31 into the upper half.  Lane 63 ends up with
 // the wave's total (summation order: a fixed tree, the same for every call).
@@ -305,6 +318,28 @@ __device__ __forceinline__ int dpp_wave_sum_i32(int v)
     v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, true);
     v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, true);
     return v;
+}
+// OR over the 64 lanes, same network: lane 63 ends up with it.
+__device__ __forceinline__ unsigned dpp_wave_or(unsigned v)
+{
+    v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);
+    v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);
+    v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);
+    v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);
+    v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, true);
+    v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, true);
+    return v;
+}
+// Pair p = b (b - 1) / 2 + a of the triangular numbering, a < b, without a table: b from a single-precision square root (exact enough
+// for p < 2^20; two integer corrections make it exact).  `root` is the caller's choice of square root: v_sqrt_f32 alone is 1 ulp,
+// which the corrections absorb; the IEEE expansion costs ~20 instructions more.
+template <typename RootFn>
+__device__ __forceinline__ void tri_pair(int p, int& a, int& b, RootFn root)
+{
+    int bb = (int)((1.0f + root(1.0f + 8.0f * (float)p)) * 0.5f);
+    if (bb * (bb - 1) / 2 > p) --bb;
+    if ((bb + 1) * bb / 2 <= p) ++bb;
+    b = bb; a = p - bb * (bb - 1) / 2;
 }
 __device__ __forceinline__ double wave_sum(double v)
 {

@@ -51,9 +51,9 @@ struct Moments {
     double S0, S1x, S1y, S1z, Sxx, Syy, Sxy, Sxz, Syz, Szz;
     __device__ __forceinline__ void load(const double* __restrict__ m)
     {
-        const double2* m2 = reinterpret_cast<const double2*>(m);
-        const double2 a = m2[0], b = m2[1], c = m2[2], d = m2[3], e = m2[4];
-        S0 = a.x; S1x = a.y; S1y = b.x; S1z = b.y; Sxx = c.x; Syy = c.y; Sxy = d.x; Sxz = d.y; Syz = e.x;
+        double M[10];
+        load_moments(m, M);
+        S0 = M[0]; S1x = M[1]; S1y = M[2]; S1z = M[3]; Sxx = M[4]; Syy = M[5]; Sxy = M[6]; Sxz = M[7]; Syz = M[8];
         Szz = S0 - Sxx - Syy;                        // the u_k are unit vectors (mw_common.hip.h, kMomStride)
     }
     template <int SIGN>

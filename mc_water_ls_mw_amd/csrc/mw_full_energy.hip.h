@@ -279,20 +279,15 @@ __device__ __forceinline__ void store_moments_wave(uint32_t* __restrict__ wq, co
     //  loop they were sixteen more registers held from group to group, in a kernel that has none to spare)
     asm volatile("" : "+v"(lane));
     auto piece = [&](int q) { return reinterpret_cast<double2*>(wq + (q >> 4) * BLOCK + (q & 15) * 4); };   // piece q of the staged half
-    auto sync = [] {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
     auto stage = [&](int h) {
         if ((lane >> 5) == h) {
 #pragma unroll
             for (int k = 0; k < 5; ++k) *piece((lane & 31) * 5 + k) = rec[k];
         }
-        sync();
+        wave_fence();
     };
     int* smol = reinterpret_cast<int*>(wq + 10 * BLOCK);
-    sync();                                              // (every lane is done with its queue column)
+    wave_fence();                                        // (every lane is done with its queue column)
     smol[lane] = mol;
     auto store = [&](int it, double2 v) {                // (each store leaves as soon as its pieces are read: nothing held but v2)
         const unsigned p = (unsigned)(it * 64 + lane), r = p / 5u, part = p - 5u * r;
@@ -304,13 +299,13 @@ __device__ __forceinline__ void store_moments_wave(uint32_t* __restrict__ wq, co
     store(1, *piece(64 + lane));
     double2 v2 = make_double2(0.0, 0.0);
     if (lane < 32) v2 = *piece(128 + lane);
-    sync();
+    wave_fence();
     stage(1);                                            // pieces 160 .. 319
     if (lane >= 32) v2 = *piece(lane - 32);
     store(2, v2);
     store(3, *piece(32 + lane));
     store(4, *piece(96 + lane));
-    sync();                                              // (the segment is the queue again)
+    wave_fence();                                        // (the segment is the queue again)
 }
 
 constexpr int kMaxGroups = 128;          // groups of 64 list columns per workgroup (chunk <= 8192)

@@ -119,7 +119,7 @@ static int launch_moves(int mode)
     const size_t iv_bytes = kMoveScratch + mw::lds_vec_bytes((size_t)g.ivcap);
     const int kmode = mode | (g.mdecl_par << 2);                          // this launch's count word of the declined list (zeroed by the
     g.mdecl_par ^= 1;                                                     // previous launch's k_move_fallback, or at allocation)
-    // The moment path (mw_move_energy.hip.h): boxes staged in LDS, no self-images, and enough requests per box to pay for the
+    // The moment path (mw_move_moments.hip.h): boxes staged in LDS, no self-images, and enough requests per box to pay for the
     // full-box pass that makes the moments (one pass costs what ~300 requests save; MW_MOVE_MOMENTS=0 | 1 overrides the count rule).
     // The moments must be those of the positions as they are NOW: they are taken from the last full-box launch only when nothing
     // that can move a molecule has run since (mw_step_launch: the full-box pass of the same step), else made here.

@@ -18,7 +18,9 @@
 //   mw_common.hip.h       constants, packed list entry, fp64 primitives, wave/DPP reductions
 //   mw_neighbours.hip.h   neighbour-list builders
 //   mw_full_energy.hip.h  full-box energy
-//   mw_move_energy.hip.h  local energy / fused trial-move energy
+//   mw_move_energy.hip.h  local energy / fused trial-move energy: k_move_energy, k_move_fallback, k_local_energy_single; includes
+//                         mw_local_energy (the plain routines), mw_move_scan (the fused scan), mw_move_moments (the moment path)
+//                         and mw_local_server.hip.h (the resident mailbox server)
 //   mw_sweep.hip.h        device-resident Monte Carlo driver (k_sweep; includes mw_sweep_common / _volume / _decide.hip.h)
 //   mw_forces.hip.h       forces and virial of the full-box energy
 //   mw_ice.hip.h          per-molecule ice structure classes (CHILL+)

@@ -124,7 +124,7 @@ __device__ __forceinline__ void dev_recipmatrix(const double* __restrict__ h, do
 }
 
 // Diagnostic build only (-DMW_SWEEP_STAMPS, tools/sweep_stamps.py): cycles of walker 0's first wavefront per phase of a round,
-// summed over the launch into g_sweep_stamps[0..15] (mw_move_energy.hip.h holds the array and the stages of one evaluation).
+// summed over the launch into g_sweep_stamps[0..15] (mw_move_scan.hip.h holds the array and the stages of one evaluation).
 #ifdef MW_SWEEP_STAMPS
 #define MW_SW_NOW() ((blockIdx.x == 0 && wv == 0) ? (unsigned long long)clock64() : 0ull)
 #define MW_SW_ACC(k, d) do { if (blockIdx.x == 0 && wv == 0 && lane == 0) g_sweep_stamps[k] += (d); } while (0)
@@ -167,12 +167,6 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-__device__ __forceinline__ void wave_fence()     // orders this wavefront's own LDS traffic for the compiler; LDS serves a wavefront in order
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 constexpr int kSweepQCap = 9;                             // in-range queue of a volume move's full-box energy: sized to fit the scratch record

@@ -65,6 +65,23 @@ def test_sweep_kernels_keep_their_register_budget(tmp_path):
 
 
 @pytest.mark.skipif(not os.path.exists(READELF), reason="llvm-readelf not in this image")
+def test_move_energy_kernels_are_the_pinned_set(tmp_path):
+    """The kernels of mw_move_energy.hip.h and mw_local_server.hip.h, by name only: k_move_energy<LDSPOS, LAYOUT, SELFIMG, MOMPATH>
+    (boxes staged in LDS with self-images, without, on the moment path; boxes gathered from global memory), k_local_server<COHERENT>
+    and the two plain kernels -- each exactly once, none besides."""
+    from mc_water_ls_mw_amd import build as mwbuild
+    mwbuild.build()
+    notes = subprocess.run([READELF, "--notes", _gfx950_code_object(tmp_path)], capture_output=True, text=True, check=True).stdout
+    names = [re.search(r"\.name:\s+(\S+)", blk).group(1) for blk in notes.split("- .agpr_count")[1:]]
+    seen = sorted(re.match(r"_ZN2mw\d+(k_[a-z_]+(?:I(?:L[bi]\d+E)+E)?)", n).group(1) for n in names
+                  if re.match(r"_ZN2mw\d+(k_move_energy|k_move_fallback|k_local_energy_single|k_local_server)(I|E)", n))
+    want = sorted(["k_move_energyILb1ELi2ELb1ELb0EE", "k_move_energyILb1ELi2ELb0ELb0EE", "k_move_energyILb1ELi2ELb0ELb1EE",
+                   "k_move_energyILb0ELi2ELb1ELb0EE", "k_local_serverILb0EE", "k_local_serverILb1EE",
+                   "k_move_fallback", "k_local_energy_single"])
+    assert seen == want, (seen, want)
+
+
+@pytest.mark.skipif(not os.path.exists(READELF), reason="llvm-readelf not in this image")
 def test_eight_small_walkers_share_a_compute_unit(tmp_path):
     """The reference's own 48-molecule Ic/Ih pair (examples/ice1_gen_weights: nbins = 101), translations only: a walker's
     static + dynamic LDS must stay within 160 KiB / 8 for the row lengths a replica farm reaches (longest row of 16 384 boxes
