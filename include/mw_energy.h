@@ -43,7 +43,7 @@ extern "C" {
 #define MW_DISPATCH_ICE      4
 #define MW_DISPATCH_RDF      5
 #define MW_DISPATCH_FAMILIES 6
-#define MW_DISPATCH_FIELDS   10
+#define MW_DISPATCH_FIELDS   13
 
 /* LDS-staged builds of mw_lds_plan */
 #define MW_LDS_ENERGY 0        /* k_model_energy, box staged in LDS (both MOMOUT builds)              */
@@ -246,7 +246,16 @@ int mw_moves_fetch(double *e_old, double *e_new);
 /* Totals over the staged moves of the last launch: out = {interactions_old, slots_old,
  * interactions_new, slots_new}.  An interaction is an in-range pair or an in-range triplet
  * slot with cos(theta) < 0.99 (molint.F90:276,361,367); a slot is one list entry visited
- * (nn(i) + sum of nn(j) over in-range j), which prices the call's algorithmic bytes. */
+ * (nn(i) + sum of nn(j) over in-range j), which prices the call's algorithmic bytes.
+ * COUNTED ON DEMAND.  A launch that takes the moment path (mw_last_dispatch: MOVES, build 3) computes energies only; this call
+ * then makes the counts with one more pass of the same kernel over the same requests (no energy written), once: a second call
+ * launches nothing.  That pass must see what the launch saw, so the counts can be asked for from the launch until the next call
+ * that replaces the requests (mw_moves_upload, mw_local_energy_batch, mw_delta_energy_batch -- whose own launch makes them
+ * available again) or that may move a molecule, change a cell or rebuild a list (position and cell uploads, mw_patch_position,
+ * mw_model_energy_of, single local-energy calls, list builds, the Monte Carlo driver).  Asked for after one of those, counts
+ * that were never made are gone: the call FAILS and says so -- it never returns stale or zero counts.  Counts already made stay
+ * readable.  Fetching energies, full-box launches and their counts do not end the claim.  MW_MOVE_COUNTS=eager (read by
+ * mw_init): the launch itself counts, as it used to, and nothing is ever pending. */
 int mw_moves_counts(long long out[4]);
 int mw_model_energy_launch(int first_ils, int count);
 /* Both launches of a step in one host call: the full-box energies of boxes first_ils .. first_ils+count-1, then the staged
@@ -380,7 +389,9 @@ int mw_sweep_lds_bytes(int nlat, int nwater, int nbins, int row_stride, int volu
  *            the boxes: persistent workgroups), moments written, dynamic LDS, workgroup size
  *   MOVES  : ivcap, requests, box staged in LDS (mlds), no self-images (m_noself), moment path, moments taken from the last
  *            full-box pass (fresh), requests per work item (mchunk), work items, dynamic LDS, build (0 L2 gather, 1 LDS with
- *            self-images, 2 LDS without, 3 moment path)
+ *            self-images, 2 LDS without, 3 moment path), counts of this launch (0 there, 1 to be made on demand by mw_moves_counts,
+ *            2 dropped), on-demand count passes launched since mw_init, requests the launch left to k_move_fallback (-1 until
+ *            mw_moves_counts has read the number back)
  *   FORCES, ICE : ivcap, boxes, box staged in LDS, workgroups per box, dynamic LDS
  *   RDF    : ivcap, boxes, small-box geometry (one wavefront per box), workgroups per box, dynamic + static LDS, images per
  *            pair (1, 3, 9 or 27: the largest of the launch's boxes)

@@ -172,6 +172,13 @@ struct Ctx {
     bool mlds = false;
     int mmode = 0;
     int m_boxlo = 0, m_boxhi = -1, m_minreq = 0;   // the uploaded requests: their boxes (0-based range) and the fewest requests any of them has
+    // The moment path's launch does not count (mw_move_energy.hip.h, mode bit 3): mw_moves_counts makes the counts of the last launch
+    // with one more pass of the same kernel over the same work items -- for as long as that pass would still count what the launch saw.
+    enum { kCountsThere = 0, kCountsPending = 1, kCountsDropped = 2 };
+    int mcnt_state = kCountsThere;     // There: d_mcnt / d_mtot hold them; Pending: to be made on demand; Dropped: a pending launch's requests,
+                                       // positions, cells or lists have changed since -- they cannot be made any more
+    int mcnt_passes = 0;               // on-demand count passes launched since mw_init
+    bool move_counts_eager = false;    // MW_MOVE_COUNTS=eager at mw_init: the launch itself counts, as it used to
     int move_moments = -1;             // MW_MOVE_MOMENTS at mw_init: -1 unset (the request-count rule), 0 scanning path, 1 moment path where admitted
     int mchunk = 16;                 // requests per work item of the uploaded batch
     bool m_noself = false;           // every box of the uploaded batch went through the cell grid: no molecule meets an image of itself
@@ -283,7 +290,10 @@ int check_boxes(int first, int count, Form form) { return form == kSingle ? chec
 // The Monte Carlo driver's moments (d_mom, swm_first / swm_count) describe positions and cells as the driver left them: every
 // entry point that writes either behind its back calls this -- under its lock, or a launch of the driver on another thread
 // could claim them again in between.
-void drop_driver_moments() { g.swm_count = 0; }
+// The same entry points end a move launch's claim to counts it has not made yet (mw_moves_counts): a count pass after them would
+// count another state than the launch evaluated.  `state_changed` = false: the full-box pass rewriting d_mom from unchanged positions.
+void drop_move_counts() { if (g.mcnt_state == Ctx::kCountsPending) g.mcnt_state = Ctx::kCountsDropped; }
+void drop_driver_moments(bool state_changed = true) { g.swm_count = 0; if (state_changed) drop_move_counts(); }
 
 // Device buffers of the context.  Every one is taken and given back here, and g.owned knows them all: a buffer allocated on
 // first use, or grown on demand, needs no entry anywhere for release_all to free it.  (Not for the single call's path, which

@@ -56,7 +56,7 @@ int launch_model_energy(int first, int count, bool with_mom = false, bool write_
         d[0] = g.ivcap; d[1] = count; d[2] = ge.lds; d[3] = ge.nsplit; d[4] = ge.chunk; d[5] = (int)grid.y; d[6] = mom != nullptr;
         d[7] = (int)ge.shmem; d[8] = ge.block;
     }
-    if (mom) { g.mom_first = first; g.mom_count = count; drop_driver_moments(); }   // (d_mom rewritten for these boxes: the driver's claim on it ends -- its launch renews it)
+    if (mom) { g.mom_first = first; g.mom_count = count; drop_driver_moments(false); }   // (d_mom rewritten for these boxes: the driver's claim on it ends -- its launch renews it)
     if (ge.nsplit > 1 && write_energy) {           // split boxes: the partials of box b live at [b*nsplit .. b*nsplit+nsplit); unsplit boxes wrote their energy themselves
         hipLaunchKernelGGL(mw::k_sum_partials, dim3(count), dim3(64), 0, g.stream, g.d_partial, g.d_cpartial,
                            g.d_energy, g.d_counts, box0, count, ge.nsplit);

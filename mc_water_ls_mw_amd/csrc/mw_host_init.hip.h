@@ -116,6 +116,8 @@ static int init_impl(int device, int nwater, int nboxes, int maxneigh)
     g.h_listbuilt.assign(nb, 0);
     { const char* fb = std::getenv("MW_FORCE_BRUTE_NEIGHBOURS"); g.force_brute = fb && *fb && *fb != '0'; }
     { const char* mm = std::getenv("MW_MOVE_MOMENTS"); g.move_moments = mm ? (mm[0] != '0' ? 1 : 0) : -1; }
+    { const char* mc = std::getenv("MW_MOVE_COUNTS"); g.move_counts_eager = mc && std::strcmp(mc, "eager") == 0; }
+    g.mcnt_state = Ctx::kCountsThere; g.mcnt_passes = 0;
     { const char* mp = std::getenv("MW_MODEL_PERSIST"); g.model_persist = !(mp && mp[0] == '0'); }
     { const char* cl = std::getenv("MW_ICE_CLUSTERS_LDS"); g.clusters_lds = !(cl && cl[0] == '0'); }
     if (dev_alloc(g.d_partial, nb * g.nsplit_max) || dev_alloc(g.d_cpartial, nb * g.nsplit_max * 2) ||

@@ -17,6 +17,15 @@ int ensure_moves(int n)
     return 0;
 }
 
+// One launch of a build of k_move_energy over the uploaded work items (the step's launch and the pass that counts on demand).
+template <typename Kernel>
+void launch_move_kernel(Kernel kernel, size_t shmem, int kmode, const double* mom, unsigned int* tot)
+{
+    hipLaunchKernelGGL(kernel, dim3(g.mwork_n), dim3(1024), shmem, g.stream,
+                       g.d_pos, g.d_ivect, g.d_nivect, g.d_listm, g.d_nn, g.d_mwork, g.d_mimol, g.d_mtrial, g.d_mperm,
+                       g.d_meold, g.d_menew, g.d_mcnt, g.d_mdecl, g.N, g.ivcap, kmode, mom, tot);
+}
+
 }  // namespace
 
 extern "C" {
@@ -26,6 +35,7 @@ int mw_moves_upload(int n, const int* ils, const int* imol, const double* trial_
     MW_LOCK;
     if (check_live()) return 1;
     if (n < 0) return fail("mw_moves_upload: n = %d", n);
+    drop_move_counts();                  // (the requests a pending count pass would read are replaced)
     g.mn = 0;
     if (n == 0) return 0;
     if (!ils || !imol) return fail("mw_moves_upload: null request arrays");
@@ -114,10 +124,11 @@ int mw_moves_upload(int n, const int* ils, const int* imol, const double* trial_
 static int launch_moves(int mode)
 {
     if (g.mn == 0) return 0;
+    g.mcnt_state = Ctx::kCountsDropped;          // (until the kernels are issued: a launch that fails on the way leaves no counts to ask for)
     if (dev_grow(g.d_mtot, g.mtot_cap, (size_t)g.mwork_n, 2 * (size_t)g.mwork_n, 4)) return 1;
     g.mtot_n = 0;
     const size_t iv_bytes = kMoveScratch + mw::lds_vec_bytes((size_t)g.ivcap);
-    const int kmode = mode | (g.mdecl_par << 2);                          // this launch's count word of the declined list (zeroed by the
+    const int kmode = mode | (g.mdecl_par << 2);                           // this launch's count word of the declined list (zeroed by the
     g.mdecl_par ^= 1;                                                     // previous launch's k_move_fallback, or at allocation)
     // The moment path (mw_move_moments.hip.h): boxes staged in LDS, no self-images, and enough requests per box to pay for the
     // full-box pass that makes the moments (one pass costs what ~300 requests save; MW_MOVE_MOMENTS=0 | 1 overrides the count rule).
@@ -129,25 +140,25 @@ static int launch_moves(int mode)
     //  pass of their own: 512 / 1280 requests per box)
     const bool use_mom = mom_ok && (g.move_moments >= 0 ? g.move_moments != 0 : g.m_minreq >= (fresh ? 512 : 1280));
     const size_t shmem = g.mlds ? move_lds_bytes(g.N, g.ivcap, g.mchunk) : iv_bytes;
-    auto launch = [&](auto kernel, const double* mom, unsigned int* tot) {
-        hipLaunchKernelGGL(kernel, dim3(g.mwork_n), dim3(1024), shmem, g.stream,
-                           g.d_pos, g.d_ivect, g.d_nivect, g.d_listm, g.d_nn, g.d_mwork, g.d_mimol, g.d_mtrial, g.d_mperm,
-                           g.d_meold, g.d_menew, g.d_mcnt, g.d_mdecl, g.N, g.ivcap, kmode, mom, tot);
-    };
+    auto launch = [&](auto kernel, const double* mom, unsigned int* tot, int bits = 0) { launch_move_kernel(kernel, shmem, kmode | bits, mom, tot); };
     if (use_mom) {
         if (!fresh && launch_model_energy(g.m_boxlo + 1, g.m_boxhi - g.m_boxlo + 1, true, false)) return 1;
-        launch(mw::k_move_energy<true, mw::kLayoutSoA, false, true>, g.d_mom, g.d_mtot);
-        g.mtot_n = g.mwork_n;
+        // the counts of the requests this kernel serves: made on demand (mw_moves_counts), by a pass of the same kernel with mode bits
+        // 3 "count" and 4 "no energy output"; MW_MOVE_COUNTS=eager: by this launch, as before
+        launch(mw::k_move_energy<true, mw::kLayoutSoA, false, true>, g.d_mom, g.d_mtot, g.move_counts_eager ? 8 : 0);
+        if (g.move_counts_eager) g.mtot_n = g.mwork_n;
     } else if (g.mlds && g.m_noself) launch(mw::k_move_energy<true, mw::kLayoutSoA, false>, nullptr, nullptr);
     else if (g.mlds)                 launch(mw::k_move_energy<true>, nullptr, nullptr);
     else                             launch(mw::k_move_energy<false>, nullptr, nullptr);
     HIPCHK(hipGetLastError());
+    g.mcnt_state = use_mom && !g.move_counts_eager ? Ctx::kCountsPending : Ctx::kCountsThere;
     {
         int* d = g.disp[MW_DISPATCH_MOVES];
         d[0] = g.ivcap; d[1] = g.mn; d[2] = g.mlds; d[3] = g.m_noself; d[4] = use_mom; d[5] = use_mom && fresh; d[6] = g.mchunk;
         d[7] = g.mwork_n; d[8] = (int)shmem; d[9] = use_mom ? 3 : (g.mlds ? (g.m_noself ? 2 : 1) : 0);
+        d[10] = g.mcnt_state; d[11] = g.mcnt_passes; d[12] = -1;
     }
-    // the requests the fused routine declined (none on ice): plain routine, one wavefront each
+    // the requests the fused routine declined (a few hundred per million on thermal ice): plain routine, one wavefront each
     hipLaunchKernelGGL(mw::k_move_fallback, dim3(std::min(1024, (g.mn + 3) / 4)), dim3(256), 0, g.stream, g.d_pos, g.d_ivect, g.d_listm, g.d_nn,
                        g.d_mimol, g.d_mtrial, g.d_mperm, g.d_meold, g.d_menew, g.d_mcnt, g.d_mdecl, g.N, g.ivcap, kmode);
     HIPCHK(hipGetLastError());
@@ -193,12 +204,27 @@ int mw_moves_counts(long long out[4])
     if (check_live()) return 1;
     out[0] = out[1] = out[2] = out[3] = 0;
     if (g.mn == 0) return 0;
+    if (g.mcnt_state == Ctx::kCountsDropped)
+        return fail("mw_moves_counts: the counts of the last launch were not made, and the launch failed or the requests, positions, cells "
+                    "or lists it saw have changed since: ask right after a launch (or run with MW_MOVE_COUNTS=eager)");
+    if (g.mcnt_state == Ctx::kCountsPending) {
+        // the launch's moment-path kernel once more, on the same work items, moments and positions: it counts what it serves (d_mtot,
+        // zeros in d_mcnt), writes no energy and appends nothing to the declined list -- whose requests k_move_fallback counted at the launch
+        launch_move_kernel(mw::k_move_energy<true, mw::kLayoutSoA, false, true>, move_lds_bytes(g.N, g.ivcap, g.mchunk), g.mmode | 8 | 16, g.d_mom, g.d_mtot);
+        HIPCHK(hipGetLastError());
+        g.mtot_n = g.mwork_n;
+        g.mcnt_state = Ctx::kCountsThere;
+        g.disp[MW_DISPATCH_MOVES][10] = g.mcnt_state; g.disp[MW_DISPATCH_MOVES][11] = ++g.mcnt_passes;
+    }
     std::vector<unsigned int> c((size_t)g.mn * 4);
     unsigned long long tot[4] = {0, 0, 0, 0};
     std::vector<unsigned int> it((size_t)g.mtot_n * 4);
     HIPCHK(hipMemcpyAsync(c.data(), g.d_mcnt, sizeof(unsigned int) * 4 * g.mn, hipMemcpyDeviceToHost, g.stream));
     if (g.mtot_n) HIPCHK(hipMemcpyAsync(it.data(), g.d_mtot, sizeof(unsigned int) * 4 * g.mtot_n, hipMemcpyDeviceToHost, g.stream));
+    int ndecl = 0;                       // (the last launch's count word of the declined list: zeroed by the NEXT launch's k_move_fallback)
+    HIPCHK(hipMemcpyAsync(&ndecl, g.d_mdecl + (g.mdecl_par ^ 1), sizeof(int), hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
+    g.disp[MW_DISPATCH_MOVES][12] = ndecl;
     for (int k = 0; k < g.mtot_n; ++k) for (int q = 0; q < 4; ++q) tot[q] += it[4 * (size_t)k + q];
     for (int m = 0; m < g.mn; ++m) {
         if (g.mmode & 1) { out[0] += c[4 * (size_t)m]; out[1] += c[4 * (size_t)m + 1]; }

@@ -613,6 +613,7 @@ int mw_sweep_translation_launch(int first_walker, int count, int nmoves, unsigne
     // the moment path of walkers entirely in LDS (mw_sweep.hip.h): 2 x L x N x kMomStride doubles of scratch per walker of the launch
     // (MW_SWEEP_MOMENTS=0: the row-scanning evaluation instead)
     double* wmom = nullptr;
+    drop_move_counts();                              // (the driver moves molecules)
     {
         const char* e = getenv("MW_SWEEP_MOMENTS");
         const int box_first = (first_walker - 1) * L + 1, nboxes = count * L;          // 1-based

@@ -19,7 +19,10 @@ namespace mw {
 // One workgroup per work item {box, first request, last request+1}: the requests are
 // sorted by box on upload, so the workgroup stages that box's positions in LDS once
 // (LDSPOS) and its 16 wavefronts then serve the item's requests from LDS gathers.
-//   mode bit 0: write e_old (mirrored positions), bit 1: write e_new (trial position)
+//   mode bit 0: write e_old (mirrored positions), bit 1: write e_new (trial position), bit 2: the declined list's count word
+//   MOMPATH only -- bit 3: count (the interactions and slots of the served requests, summed per item into `mtot`, and the zero words
+//   of `counts`: without it the launch computes and writes nothing of them), bit 4: no energy output (nothing written to e_old or
+//   e_new, nothing appended to `declined`: the pass that counts on demand, mw_moves_counts)
 constexpr int kMoveChunk = 2048;   // requests per work item when the box is staged in LDS
 
 // (LAYOUT: SoA measures 1.4 % faster than the paired layout here -- 1288 vs 1306 us, tools/kbench -- now that the scan
@@ -56,6 +59,7 @@ void k_move_energy(const double* __restrict__ pos, const double* __restrict__ iv
     const int4 w = work[blockIdx.x];
     const int b = w.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool count = !MOMPATH || (mode & 8) != 0, quiet = MOMPATH && (mode & 16) != 0;
     const double* P  = pos + (size_t)b * N * 3;
     const double* IV = ivect + (size_t)b * ivcap * 3;
     const uint32_t* LM = listm + (size_t)b * N * kRow;
@@ -136,26 +140,26 @@ void k_move_energy(const double* __restrict__ pos, const double* __restrict__ iv
 
         MoveRes r;
         bool fast;
-        if constexpr (MOMPATH) fast = move_energy_mom_wave<false, 0, MW_MOVE_WHEN>(getpos, getiv, nnof, mom + (size_t)b * N * kMomStride, ws, s_ptab, i, nnof(i), e, xo, yo, zo, xn, yn, zn, lane, r, acc);
+        if constexpr (MOMPATH) fast = move_energy_mom_wave<false, 0, MW_MOVE_WHEN>(getpos, getiv, nnof, mom + (size_t)b * N * kMomStride, ws, s_ptab, i, nnof(i), e, xo, yo, zo, xn, yn, zn, lane, r, acc, nullptr, nullptr, nullptr, nullptr, count);
         else fast = move_energy_wave<SELFIMG>(getpos, getiv, row, nnof, ws, niv, i, nnof(i), e, xo, yo, zo, xn, yn, zn, lane, r);
         if (!fast) {
             // a request the fused routine declines (a row longer than 32 entries, more than kCap in-range neighbours, a
             // molecule that neighbours its own image -- never on ice) is left to k_move_fallback: with the plain routine
             // inlined here its registers counted against this loop (37 scalar registers spilled to vector lanes, ~30
             // vector instructions per request on moving them), and calling it out of line costs scratch (+8 % time)
-            if (lane == 0) {
+            if (lane == 0 && !quiet) {
                 const int k = atomicAdd(&declined[(mode >> 2) & 1], 1);
                 declined[2 + 2 * k] = m; declined[3 + 2 * k] = b;
             }
         } else if (lane == 0) {
             const size_t o = (size_t)perm[m];
             if constexpr (MOMPATH) { r.io = r.so = r.in_ = r.sn = 0u; }       // (the counts of served requests go to `mtot`, summed per work item)
-            if (mode & 1) { e_old[o] = r.eo; counts[4 * o] = r.io; counts[4 * o + 1] = r.so; }
-            if (mode & 2) { e_new[o] = r.en; counts[4 * o + 2] = r.in_; counts[4 * o + 3] = r.sn; }
+            if (mode & 1) { if (!quiet) e_old[o] = r.eo; if (count) { counts[4 * o] = r.io; counts[4 * o + 1] = r.so; } }
+            if (mode & 2) { if (!quiet) e_new[o] = r.en; if (count) { counts[4 * o + 2] = r.in_; counts[4 * o + 3] = r.sn; } }
         }
         cur = nxt; i = i_nx; e = e_nx; tx = tx_nx; ty = ty_nx; tz = tz_nx;
     }
-    if constexpr (MOMPATH) {         // the item's counts: lanes -> wavefront -> workgroup, ONE plain store per item (thousands of wavefronts adding to
+    if constexpr (MOMPATH) if (count) {   // the item's counts: lanes -> wavefront -> workgroup, ONE plain store per item (thousands of wavefronts adding to
         __shared__ unsigned int s_tot[16][4];                              // four global words serialise: +0.3 ms on a 0.9 ms launch)
 #pragma unroll
         for (int c = 0; c < 4; ++c) {

@@ -29,7 +29,8 @@ namespace mw {
 // -------------------------------------------------------------------------------------
 // `ptab[p]` = (a | b << 8) of the p-th pair a < b (a table in LDS: decoding p costs a dozen instructions otherwise).  The interaction
 // and slot counts are ADDED, lane by lane, to `acc` = {interactions old, slots old, interactions new, slots new}: the caller sums
-// them over the lanes once per work item instead of once per request.
+// them over the lanes once per work item instead of once per request -- when `count` (wave-uniform) is set: without it nothing of the
+// counts is computed, not the rows' lengths, not the slot sums, not `acc` (the batched kernel counts on demand, in a pass of its own).
 //
 // SWEEP = true: the Monte Carlo driver's small walkers (mw_sweep.hip.h), whose cells are narrower than three list radii and whose
 // moments change under the routine's feet.  (1) A neighbour j that is in range through TWO of its images holds two contributions of
@@ -52,7 +53,7 @@ __device__ __forceinline__ bool move_energy_mom_wave(PosFn getpos, IvFn getiv, N
                                                      double xo, double yo, double zo, double xn, double yn, double zn,
                                                      int lane, MoveRes& res, unsigned int (&acc)[4], int* cnt_u = nullptr,
                                                      const unsigned long long* __restrict__ lmask = nullptr, const int* oth = nullptr,
-                                                     unsigned* cmask = nullptr)
+                                                     unsigned* cmask = nullptr, bool count = true)
 {
     // ---- pass 0: as move_energy_wave -- lanes 0..31 slot l of i's row against the OLD position, lanes 32..63 against the TRIAL one
 #ifdef MW_SWEEP_STAMPS
@@ -79,7 +80,7 @@ __device__ __forceinline__ bool move_energy_mom_wave(PosFn getpos, IvFn getiv, N
     getiv(kimg, jvx, jvy, jvz);
     [[maybe_unused]] unsigned long long lmj = 0ull;
     if constexpr (NOTH > 0) lmj = lmask != nullptr ? lmask[j] : 0ull;
-    const int nnj = (has && !SWEEP) ? nnof(j) : 0;
+    const int nnj = (has && !SWEEP && count) ? nnof(j) : 0;
     const double qx = xj + jvx, qy = yj + jvy, qz = zj + jvz;                 // molint.F90:269
     const double rix = half ? xn : xo, riy = half ? yn : yo, riz = half ? zn : zo;
     const double ax = qx - rix, ay = qy - riy, az = qz - riz;                 // :272
@@ -132,19 +133,19 @@ __device__ __forceinline__ bool move_energy_mom_wave(PosFn getpos, IvFn getiv, N
         double S0 = M[0], S1x = M[1], S1y = M[2], S1z = M[3];
         double Sxx = M[4], Syy = M[5], Sxy = M[6], Sxz = M[7], Syz = M[8];
         double Szz = (S0 - Sxx) - Syy;                       // (trace of sum g u u^T = sum g)
-        double cn = M[9];
+        double cn = count ? M[9] : 0.0;
         if ((mo_ >> sl) & 1u) {      // j's moments hold i at its mirrored (old) position: that term is not a third body
             const double ux = (xo - qx) * r_old, uy = (yo - qy) * r_old, uz = (zo - qz) * r_old;   // unit vector j -> i (old)
             const double hx = g_old * ux, hy = g_old * uy, hz = g_old * uz;
             S0 -= g_old; S1x -= hx; S1y -= hy; S1z -= hz;
             Sxx -= hx * ux; Syy -= hy * uy; Szz -= hz * uz; Sxy -= hx * uy; Sxz -= hx * uz; Syz -= hy * uz;
-            cn -= 1.0;
+            if (count) cn -= 1.0;
         }
         const double vx = -ax * rinv, vy = -ay * rinv, vz = -az * rinv;                            // unit vector j -> i, this geometry
         const double wx = Sxx * vx + Sxy * vy + Sxz * vz, wy = Sxy * vx + Syy * vy + Syz * vz, wz = Sxz * vx + Syz * vy + Szz * vz;
         const double quad = vx * wx + vy * wy + vz * wz, lin = vx * S1x + vy * S1y + vz * S1z;
         t3 = g * ((quad - 2.0 * kCos0 * lin) + kCos0 * kCos0 * S0);                                // :324-343,385-387 summed over k
-        nt = (unsigned int)(cn + 0.5);
+        if (count) nt = (unsigned int)(cn + 0.5);
     }
     wave_fence();
 
@@ -185,7 +186,7 @@ __device__ __forceinline__ bool move_energy_mom_wave(PosFn getpos, IvFn getiv, N
         const double ra = rinvq[ia], rb = rinvq[b];
         const double Ax = rqx - pax, Ay = rqy - pay, Az = rqz - paz, Bx = rqx - pbx, By = rqy - pby, Bz = rqz - pbz;
         const double ct = ((Ax * Bx + Ay * By + Az * Bz) * ra) * rb;                               // :316,365
-        if (act && ct < 0.99) { const double d = ct - kCos0; t3p += gvq[ia] * (gvq[b] * (d * d)); ++ntp; }   // :367-368,385-387
+        if (act && ct < 0.99) { const double d = ct - kCos0; t3p += gvq[ia] * (gvq[b] * (d * d)); if (count) ++ntp; }   // :367-368,385-387
         if constexpr (SWEEP) anysame |= __ballot(live && (fa >> 2) == (fb >> 2));      // two records of ONE molecule: see below
         // a and b as each other's third bodies: only when they lie within the cutoff of each other -- on ice a molecule's in-range
         // neighbours do not (first shell 2.76 A, its members 4.5 A apart, cutoff 4.31 A), so the wavefront usually skips this
@@ -243,7 +244,7 @@ __device__ __forceinline__ bool move_energy_mom_wave(PosFn getpos, IvFn getiv, N
     dpp_wave_sum2(kLamEps * ((gq == 0 ? t3p : 0.0) + (half == 0 ? t3 : 0.0)) + (half == 0 ? accp : 0.0),
                   kLamEps * ((gq == 1 ? t3p : 0.0) + (half == 1 ? t3 : 0.0)) + (half == 1 ? accp : 0.0), eo, en);
     res.eo = eo; res.en = en;
-    if constexpr (!SWEEP) {
+    if (!SWEEP && count) {
         // this request's interactions (in-range pairs + triplet slots that contribute) and list slots (n_i + the rows of its in-range
         // neighbours: what prices its algorithmic bytes), left in the lanes that know them
         const unsigned int ci = (in ? 1u : 0u) + nt, cs = (in ? (unsigned int)nnj : 0u) + (sl == 0 ? (unsigned int)n_i : 0u);

@@ -60,10 +60,13 @@ ABI_SYMBOLS = (
 )
 
 #: the kernel families of mw_last_dispatch (MW_DISPATCH_*, by index) and the names of the fields it reports for each
+#: ("moves": the last three fields follow the counts of that launch, not the launch alone -- ``moves_counts()`` updates them:
+#: "counts" 0 there / 1 to be made on demand / 2 dropped, "count_passes" the on-demand passes since ``energy_init``, "declined"
+#: the requests the launch left to the fallback kernel, -1 until ``moves_counts()`` has read the number back)
 DISPATCH_FIELDS = {
     "build": ("ivcap", "boxes", "grid_boxes", "brute_boxes", "fused_sort", "legacy_search", "order_seg", "nseg", "lds_bytes"),
     "energy": ("ivcap", "boxes", "lds", "nsplit", "chunk", "grid_y", "moments", "lds_bytes", "block"),
-    "moves": ("ivcap", "requests", "mlds", "noself", "use_mom", "fresh", "mchunk", "items", "lds_bytes", "build"),
+    "moves": ("ivcap", "requests", "mlds", "noself", "use_mom", "fresh", "mchunk", "items", "lds_bytes", "build", "counts", "count_passes", "declined"),
     "forces": ("ivcap", "boxes", "lds", "nsplit", "lds_bytes"),
     "ice": ("ivcap", "boxes", "lds", "nsplit", "lds_bytes"),
     "rdf": ("ivcap", "boxes", "small", "workgroups_per_box", "lds_bytes", "images"),
@@ -587,7 +590,13 @@ class EnergyModule:
         return eo, en
 
     def moves_counts(self):
-        """(interactions_old, slots_old, interactions_new, slots_new) summed over the staged moves."""
+        """(interactions_old, slots_old, interactions_new, slots_new) summed over the staged moves of the last launch.
+
+        They come from the move kernels themselves, counted ON DEMAND: a launch on the moment path computes energies only, and
+        the first call here runs the same kernel once more over the same requests to count (a second call launches nothing).
+        Ask between the launch and the next call that replaces the requests (``moves_upload``, ``local_energy_batch``,
+        ``delta_energy_batch``) or that may move a molecule, change a cell or rebuild a list; after one of those, counts that
+        were never made raise ``MwError``.  ``MW_MOVE_COUNTS=eager`` (at ``energy_init``) makes the launch count, as it used to."""
         out = (ctypes.c_longlong * 4)()
         self._chk(self.L.mw_moves_counts(out))
         return tuple(int(v) for v in out)
