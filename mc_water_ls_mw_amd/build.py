@@ -1,5 +1,5 @@
-"""Build libmw_hip.so (the C-ABI engine) and libmw_comms.so (the RCCL exchange layer for a Fortran host, include/mw_comms.h)
-in-tree with hipcc for gfx950.
+"""Build libmw_hip.so (the C-ABI engine), libmw_comms.so (the RCCL exchange layer for a Fortran host, include/mw_comms.h)
+and libmw_sk.so (the structure factor S(k), include/mw_sk.h) in-tree with hipcc for gfx950.
 
     python -m mc_water_ls_mw_amd.build [--force]
 
@@ -27,6 +27,11 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 COMMS_LIB = os.path.join(PKG, "libmw_comms.so")
 COMMS_SRC = os.path.join(CSRC, "mw_comms.hip")
 COMMS_DEPS = [COMMS_SRC, os.path.join(os.path.dirname(PKG), "include", "mw_comms.h")]
+
+
+SK_LIB = os.path.join(PKG, "libmw_sk.so")
+SK_SRC = os.path.join(CSRC, "mw_sk.hip")
+SK_DEPS = [SK_SRC, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_sk.h")]
 
 
 def hipcc_path():
@@ -69,7 +74,20 @@ def build_comms(force=False, verbose=False):
     return COMMS_LIB
 
 
+def build_sk(force=False, verbose=False):
+    """libmw_sk.so: the structure-factor kernels and their C ABI, a translation unit of its own (libmw_hip.so's code object
+    and symbols do not move with it)."""
+    if not force and os.path.exists(SK_LIB) and all(os.path.getmtime(p) <= os.path.getmtime(SK_LIB) for p in SK_DEPS):
+        return SK_LIB
+    cmd = [hipcc_path(), *HIPCC_FLAGS, "-o", SK_LIB, SK_SRC]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return SK_LIB
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv, verbose=True)
     print(LIB)
     print(build_comms(force="--force" in sys.argv, verbose=True))
+    print(build_sk(force="--force" in sys.argv, verbose=True))

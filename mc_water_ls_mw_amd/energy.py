@@ -479,6 +479,21 @@ class EnergyModule:
         """(r_ang, g, n) of lattice ils: rdf_from_counts of rdf_counts with this module's volume[ils - 1]."""
         return rdf_from_counts(self.rdf_counts(ils, r_max_ang, nbins), self.nwater, self.volume[ils - 1], r_max_ang)
 
+    # -- static structure factor S(k) (libmw_sk.so, include/mw_sk.h; no counterpart in the reference) ------------
+    def structure_factor(self, first_ils=1, count=None, nvec=None, want_rho=False):
+        """S [count, M] (with ``want_rho`` also rho, complex [count, M]) of ``count`` boxes for the integer triples ``nvec``
+        [M, 3] (structure.kvectors), from the positions the DEVICE holds and this module's hmatrix (after device volume
+        moves call ``WalkerFarm.sync_cells`` first).  The positions take one host hop (mw_download_positions_range, 24 bytes
+        per molecule) on their way to libmw_sk.so, which shares nothing with the engine but the device."""
+        from . import structure
+        if nvec is None:
+            raise MwError("structure_factor: nvec is required (structure.kvectors makes the triples of a cell)")
+        count = self.num_lattices - first_ils + 1 if count is None else count
+        self._ils(first_ils), self._ils(first_ils + count - 1)
+        pos = np.zeros((count, self.nwater, 3))
+        self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
+        return structure.structure_factor(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, nvec, want_rho=want_rho)
+
     def model_energy_counts(self, ils):
         p, t = ctypes.c_longlong(0), ctypes.c_longlong(0)
         self._chk(self.L.mw_model_energy_counts(ils, ctypes.byref(p), ctypes.byref(t)))

@@ -324,6 +324,26 @@ class WalkerFarm:
         shape = (self.nwalkers, self.nlat, int(nbins))
         return r, g.reshape(shape).mean(axis=0), n.reshape(shape).mean(axis=0)
 
+    def structure_factor(self, k_max_ang=3.0, nvec=None):
+        """(nvec int32 [M, 3], S_mean [nlat, M], klen [nlat, M]): the static structure factor of every lattice, averaged over
+        the walkers on the device (mw_sk_mean, libmw_sk.so), from the positions and cells the device holds (the cells read
+        back through :meth:`sync_cells` first).  ``nvec``: the integer triples to evaluate; by default the half-space
+        triples of lattice 1's walker-mean cell up to ``k_max_ang`` (1 / Angstrom).  A triple n labels the same reflection
+        in every walker, but under NPT each walker's cell differs: ``klen`` is |k_n| (1 / Angstrom) of the WALKER-MEAN cell
+        of each lattice, a label for the mean, not the |k| of any one walker."""
+        from . import structure
+        self.sync_cells()
+        em = self.em
+        hmean = em.hmatrix.reshape(self.nwalkers, self.nlat, 3, 3).mean(axis=0)
+        if nvec is None:
+            nvec = structure.kvectors(hmean[0], k_max_ang, half=True)
+        nvec = np.ascontiguousarray(nvec, dtype=np.int32)
+        pos = np.zeros((em.num_lattices, em.nwater, 3))
+        em._chk(self.L.mw_download_positions_range(1, em.num_lattices, pos.ctypes.data_as(_dp)))
+        smean = structure.structure_factor_mean(em.hmatrix, pos, nvec, self.nlat)
+        klen = np.stack([structure.k_lengths(hmean[g], nvec) for g in range(self.nlat)])
+        return nvec, smean, klen
+
     # -- chain synchronisation (mc_check_chain_synchronisation, mc_moves.F90:2217-2416) -------------------------
     def set_reference(self):
         """Remember the reference configuration (ref_hmatrix / ref_ljr of init.f90:90,106) from the host's current
