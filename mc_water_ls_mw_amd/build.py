@@ -1,5 +1,6 @@
 """Build libmw_hip.so (the C-ABI engine), libmw_comms.so (the RCCL exchange layer for a Fortran host, include/mw_comms.h)
-and libmw_sk.so (the structure factor S(k), include/mw_sk.h) in-tree with hipcc for gfx950.
+libmw_sk.so (the structure factor S(k), include/mw_sk.h) and libmw_boo.so (the Steinhardt bond-order parameters,
+include/mw_boo.h) in-tree with hipcc for gfx950.
 
     python -m mc_water_ls_mw_amd.build [--force]
 
@@ -32,6 +33,11 @@ COMMS_DEPS = [COMMS_SRC, os.path.join(os.path.dirname(PKG), "include", "mw_comms
 SK_LIB = os.path.join(PKG, "libmw_sk.so")
 SK_SRC = os.path.join(CSRC, "mw_sk.hip")
 SK_DEPS = [SK_SRC, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_sk.h")]
+
+
+BOO_LIB = os.path.join(PKG, "libmw_boo.so")
+BOO_SRC = os.path.join(CSRC, "mw_boo.hip")
+BOO_DEPS = [BOO_SRC, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_boo.h")]
 
 
 def hipcc_path():
@@ -86,8 +92,20 @@ def build_sk(force=False, verbose=False):
     return SK_LIB
 
 
+def build_boo(force=False, verbose=False):
+    """libmw_boo.so: the bond-order kernels and their C ABI, a translation unit of its own like libmw_sk.so."""
+    if not force and os.path.exists(BOO_LIB) and all(os.path.getmtime(p) <= os.path.getmtime(BOO_LIB) for p in BOO_DEPS):
+        return BOO_LIB
+    cmd = [hipcc_path(), *HIPCC_FLAGS, "-o", BOO_LIB, BOO_SRC]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return BOO_LIB
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv, verbose=True)
     print(LIB)
     print(build_comms(force="--force" in sys.argv, verbose=True))
     print(build_sk(force="--force" in sys.argv, verbose=True))
+    print(build_boo(force="--force" in sys.argv, verbose=True))

@@ -494,6 +494,19 @@ class EnergyModule:
         self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
         return structure.structure_factor(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, nvec, want_rho=want_rho)
 
+    # -- Steinhardt bond order (libmw_boo.so, include/mw_boo.h; no counterpart in the reference) -------------------
+    def bond_order(self, first_ils=1, count=None, rc_ang=3.5, threshold=0.5):
+        """(q [count, nwater, 4], nn [count, nwater, 2], summary [count, 4]) of ``count`` boxes -- bondorder.bond_order -- from
+        the positions the DEVICE holds and this module's hmatrix (after device volume moves call ``WalkerFarm.sync_cells``
+        first).  The positions take one host hop (mw_download_positions_range) on their way to libmw_boo.so, which shares
+        nothing with the engine but the device."""
+        from . import bondorder
+        count = self.num_lattices - first_ils + 1 if count is None else count
+        self._ils(first_ils), self._ils(first_ils + count - 1)
+        pos = np.zeros((count, self.nwater, 3))
+        self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
+        return bondorder.bond_order(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, rc_ang, threshold)
+
     def model_energy_counts(self, ils):
         p, t = ctypes.c_longlong(0), ctypes.c_longlong(0)
         self._chk(self.L.mw_model_energy_counts(ils, ctypes.byref(p), ctypes.byref(t)))

@@ -344,6 +344,17 @@ class WalkerFarm:
         klen = np.stack([structure.k_lengths(hmean[g], nvec) for g in range(self.nlat)])
         return nvec, smean, klen
 
+    def bond_order(self, rc_ang=3.5, threshold=0.5):
+        """(summary [nwalkers, nlat, 4], solid [nwalkers, nlat]): (Q4, Q6, <qbar4>, <qbar6>) of every lattice of every walker
+        and the fraction of its molecules with at least three solid-like connections (s_ij > ``threshold``), from the
+        positions and cells the device holds (the cells read back through :meth:`sync_cells` first).  The continuous
+        companion of :meth:`ice_fractions`: qbar6 and Q6 show a lattice drifting towards disorder long before a CHILL+
+        class flips."""
+        self.sync_cells()
+        _, nn, summary = self.em.bond_order(1, self.em.num_lattices, rc_ang, threshold)
+        solid = (nn[:, :, 1] >= 3).sum(axis=1) / float(self.em.nwater)
+        return summary.reshape(self.nwalkers, self.nlat, 4), solid.reshape(self.nwalkers, self.nlat)
+
     # -- chain synchronisation (mc_check_chain_synchronisation, mc_moves.F90:2217-2416) -------------------------
     def set_reference(self):
         """Remember the reference configuration (ref_hmatrix / ref_ljr of init.f90:90,106) from the host's current
