@@ -158,7 +158,7 @@ static int launch_moves(int mode)
         d[7] = g.mwork_n; d[8] = (int)shmem; d[9] = use_mom ? 3 : (g.mlds ? (g.m_noself ? 2 : 1) : 0);
         d[10] = g.mcnt_state; d[11] = g.mcnt_passes; d[12] = -1;
     }
-    // the requests the fused routine declined (a few hundred per million on thermal ice): plain routine, one wavefront each
+    // the requests the fused routine declined (a few hundred per million on thermal ice): batched routine, two wavefronts each (one per position)
     hipLaunchKernelGGL(mw::k_move_fallback, dim3(std::min(1024, (g.mn + 3) / 4)), dim3(256), 0, g.stream, g.d_pos, g.d_ivect, g.d_listm, g.d_nn,
                        g.d_mimol, g.d_mtrial, g.d_mperm, g.d_meold, g.d_menew, g.d_mcnt, g.d_mdecl, g.N, g.ivcap, kmode);
     HIPCHK(hipGetLastError());

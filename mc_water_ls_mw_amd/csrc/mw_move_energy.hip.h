@@ -116,32 +116,49 @@ void k_move_energy(const double* __restrict__ pos, const double* __restrict__ iv
     // molecule's own row right away -- a request never begins by waiting on memory, and a wavefront that drew
     // cheap requests simply serves more of them (static dealing left ~8 % of the wave-time idle at the item's end).
     // (Without LDS staging an item holds at most 16 requests: one per wavefront.)
+    // What a request brings with it from global memory -- entry (lane & 31) of its molecule's row, its trial position (lane c < 3
+    // holds component c) and its slot in the caller's order, perm[] -- is asked for ONE REQUEST AHEAD with vector loads: the
+    // addresses of the last two are the same in every lane, and as scalar loads they would share their counter with the LDS reads,
+    // which return in another order -- the next LDS read would wait for them, at the start of the evaluation they were meant to
+    // hide behind (in_lanes() keeps the compiler from seeing that).  They are first used after the evaluation.  (On the moment path
+    // the evaluation's own wait for the moments, ~130 instructions on, takes them in: the vector-memory counter counts in order and
+    // they were issued first.  What is gained there is that nothing waits for them at the request's START.)
+    // (Offsets in 32 bits, so that the loads take a scalar base: mw_moves_upload's request count is an int, and 3 x it as unsigned
+    // holds up to 1.4e9 requests -- 34 GB of trial positions.)
+    auto in_lanes = [](int v) { asm volatile("" : "+v"(v)); return v; };
+    auto fetch = [&](int q, int& i_, uint32_t& e_, double& t_, int& o_) {
+        i_ = 0; e_ = 0u; t_ = 0.0; o_ = 0;
+        if (q < nreq) {
+            const int m_ = in_lanes(w.y + q);
+            i_ = imol_of(q); e_ = row(i_, lane & 31);
+            if (mode & 2) t_ = req_trial[3u * (unsigned)m_ + (lane < 3 ? (unsigned)lane : 0u)];
+            o_ = perm[(unsigned)m_];
+        }
+    };
     int cur = wave;
-    int i = cur < nreq ? imol_of(cur) : 0;
-    uint32_t e = cur < nreq ? row(i, lane & 31) : 0u;
-    double tx = 0.0, ty = 0.0, tz = 0.0;                     // the request's trial position, fetched with its row entry
-    if ((mode & 2) && cur < nreq) { const double* t3 = req_trial + 3 * (size_t)(w.y + cur); tx = t3[0]; ty = t3[1]; tz = t3[2]; }
+    int i, o; uint32_t e; double t;
+    fetch(cur, i, e, t, o);
     while (cur < nreq) {
         int nxt = 0;
         if (lane == 0) nxt = __hip_atomic_fetch_add(&s_next, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         nxt = LDSPOS ? __builtin_amdgcn_readfirstlane(nxt) : nreq;
-        int i_nx = 0; uint32_t e_nx = 0u;
-        double tx_nx = 0.0, ty_nx = 0.0, tz_nx = 0.0;
-        if (nxt < nreq) {
-            i_nx = imol_of(nxt); e_nx = row(i_nx, lane & 31);
-            if (mode & 2) { const double* t3 = req_trial + 3 * (size_t)(w.y + nxt); tx_nx = t3[0]; ty_nx = t3[1]; tz_nx = t3[2]; }
-        }
+        int i_nx, o_nx; uint32_t e_nx; double t_nx;
+        fetch(nxt, i_nx, e_nx, t_nx, o_nx);
 
         const int m = w.y + cur;
         double xo, yo, zo;
         getpos(i, xo, yo, zo);
         double xn = xo, yn = yo, zn = zo;
-        if (mode & 2) { xn = tx; yn = ty; zn = tz; }
+        if (mode & 2) { xn = readlane_f64(t, 0); yn = readlane_f64(t, 1); zn = readlane_f64(t, 2); }
 
         MoveRes r;
         bool fast;
         if constexpr (MOMPATH) fast = move_energy_mom_wave<false, 0, MW_MOVE_WHEN>(getpos, getiv, nnof, mom + (size_t)b * N * kMomStride, ws, s_ptab, i, nnof(i), e, xo, yo, zo, xn, yn, zn, lane, r, acc, nullptr, nullptr, nullptr, nullptr, count);
         else fast = move_energy_wave<SELFIMG>(getpos, getiv, row, nnof, ws, niv, i, nnof(i), e, xo, yo, zo, xn, yn, zn, lane, r);
+        // (the next request's three values are taken HERE, ahead of the result stores: taken at the loop's end, the wait for them would
+        //  also wait for those stores to be acknowledged, once per request.  On the scan path this is where they are waited for; on
+        //  the moment path they have arrived with the moments and this only fixes the place)
+        asm volatile("" : "+v"(e_nx), "+v"(t_nx), "+v"(o_nx));
         if (!fast) {
             // a request the fused routine declines (a row longer than 32 entries, more than kCap in-range neighbours, a
             // molecule that neighbours its own image -- never on ice) is left to k_move_fallback: with the plain routine
@@ -152,12 +169,12 @@ void k_move_energy(const double* __restrict__ pos, const double* __restrict__ iv
                 declined[2 + 2 * k] = m; declined[3 + 2 * k] = b;
             }
         } else if (lane == 0) {
-            const size_t o = (size_t)perm[m];
+            const size_t so = (size_t)o;
             if constexpr (MOMPATH) { r.io = r.so = r.in_ = r.sn = 0u; }       // (the counts of served requests go to `mtot`, summed per work item)
-            if (mode & 1) { if (!quiet) e_old[o] = r.eo; if (count) { counts[4 * o] = r.io; counts[4 * o + 1] = r.so; } }
-            if (mode & 2) { if (!quiet) e_new[o] = r.en; if (count) { counts[4 * o + 2] = r.in_; counts[4 * o + 3] = r.sn; } }
+            if (mode & 1) { if (!quiet) e_old[so] = r.eo; if (count) { counts[4 * so] = r.io; counts[4 * so + 1] = r.so; } }
+            if (mode & 2) { if (!quiet) e_new[so] = r.en; if (count) { counts[4 * so + 2] = r.in_; counts[4 * so + 3] = r.sn; } }
         }
-        cur = nxt; i = i_nx; e = e_nx; tx = tx_nx; ty = ty_nx; tz = tz_nx;
+        cur = nxt; i = i_nx; e = e_nx; t = t_nx; o = o_nx;
     }
     if constexpr (MOMPATH) if (count) {   // the item's counts: lanes -> wavefront -> workgroup, ONE plain store per item (thousands of wavefronts adding to
         __shared__ unsigned int s_tot[16][4];                              // four global words serialise: +0.3 ms on a 0.9 ms launch)
@@ -175,8 +192,14 @@ void k_move_energy(const double* __restrict__ pos, const double* __restrict__ iv
     }
 }
 
-// The requests k_move_energy declined, one wavefront each with the plain routine (positions and rows from global memory).
+// The requests k_move_energy declined: TWO wavefronts each, one for the mirrored (old) and one for the trial position, and only the
+// sides `mode` asks for.  Each evaluates with local_energy_wave_batched -- the rows and third-body positions of up to eight in-range
+// neighbours in flight together: four dependent round trips to global memory where the neighbour-by-neighbour routine makes three
+// per in-range neighbour, same terms in the same per-lane order -- and writes its own energy and its own two count words.
 //   grid = any, block = 256; exits at once when nothing was declined
+// (The batched routine reads all 64 slots of a row whatever its length, and the positions and image vectors the slots past the end
+// name: the list is allocated zeroed and only ever holds valid entries, mw_host_init.hip.h -- this kernel depends on that as the
+// resident server does.)
 // The list has two count words used by alternate launches (mode bit 2): this kernel zeroes the OTHER one, which the next
 // launch's k_move_energy will count in -- a memset per launch (a fill kernel and its dispatch gap, ~10 us) is saved.
 __global__ __launch_bounds__(256)
@@ -191,23 +214,24 @@ void k_move_fallback(const double* __restrict__ pos, const double* __restrict__ 
     if (blockIdx.x == 0 && threadIdx.x == 0) declined[par ^ 1] = 0;
     const int lane = threadIdx.x & 63;
     const int wave = (int)(blockIdx.x * (blockDim.x >> 6)) + (int)(threadIdx.x >> 6), nwaves = (int)(gridDim.x * (blockDim.x >> 6));
-    for (int k = wave; k < n; k += nwaves) {
-        const int m = declined[2 + 2 * k], b = declined[3 + 2 * k];
+    for (int k = wave; k < 2 * n; k += nwaves) {
+        const int side = k & 1;                               // 0: the mirrored position, 1: the trial position
+        if (!((mode >> side) & 1)) continue;
+        const int m = declined[2 + 2 * (k >> 1)], b = declined[3 + 2 * (k >> 1)];
         const double* P  = pos + (size_t)b * N * 3;
         const double* IV = ivect + (size_t)b * ivcap * 3;
         const uint32_t* LM = listm + (size_t)b * N * kRow;
         const int* NN = nn + (size_t)b * N;
         const int i = req_imol[m];
+        const size_t o = (size_t)perm[m];
         Override none; none.idx = -1; none.x = none.y = none.z = 0.0;
         Override tr; tr.idx = -1; tr.x = tr.y = tr.z = 0.0;
-        if (mode & 2) { tr.idx = i; tr.x = req_trial[3 * (size_t)m]; tr.y = req_trial[3 * (size_t)m + 1]; tr.z = req_trial[3 * (size_t)m + 2]; }
-        MoveRes r;
-        r.eo = local_energy_wave(P, IV, LM, NN, i, none, none, lane, r.io, r.so);
-        r.en = local_energy_wave(P, IV, LM, NN, i, tr, none, lane, r.in_, r.sn);
+        if (side) { tr.idx = i; tr.x = req_trial[3 * (size_t)m]; tr.y = req_trial[3 * (size_t)m + 1]; tr.z = req_trial[3 * (size_t)m + 2]; }
+        unsigned int ni, ns;
+        const double en = local_energy_wave_batched<false>(P, IV, LM, NN, i, tr, none, lane, ni, ns);
         if (lane == 0) {
-            const size_t o = (size_t)perm[m];
-            if (mode & 1) { e_old[o] = r.eo; counts[4 * o] = r.io; counts[4 * o + 1] = r.so; }
-            if (mode & 2) { e_new[o] = r.en; counts[4 * o + 2] = r.in_; counts[4 * o + 3] = r.sn; }
+            (side ? e_new : e_old)[o] = en;
+            counts[4 * o + 2 * side] = ni; counts[4 * o + 2 * side + 1] = ns;
         }
     }
 }
