@@ -56,7 +56,9 @@
  *
  * Every function returns 0, or nonzero with the reason in mw_boo_last_error().  A rejected call launches nothing and writes
  * nothing; its message names the argument, and box indices in messages count from 0.  Arguments are checked before the
- * library's state, so a call with bad arguments says so with or without a device.
+ * library's state, so a call with bad arguments says so with or without a device.  The library lives on the device given to
+ * mw_boo_init: every function that touches it makes that device current for the call and puts the caller's current device
+ * back before it returns.
  */
 #ifndef MW_BOO_H
 #define MW_BOO_H
@@ -67,7 +69,8 @@ extern "C" {
 
 #define MW_BOO_PLAN_FIELDS 9
 
-/* Without a HIP device: fails with "no HIP device" (there is no CPU fallback).  device < 0: device 0. */
+/* Without a HIP device: fails with "no HIP device" (there is no CPU fallback).  device < 0: device 0.  A failed init
+ * gives back the stream and events it made and leaves the library not initialised. */
 int mw_boo_init(int device);
 int mw_boo_finalize(void);
 int mw_boo_is_initialised(void);

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from .energy import MwError, _share_hip_runtime_with_torch
+from ._devlib import DevLib, MwError, check_boxes, check_device_tensors, host_boxes
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 BOO_LIB_PATH = os.path.join(PKG, "libmw_boo.so")
@@ -26,92 +26,44 @@ BOO_ABI_SYMBOLS = ("mw_boo_init", "mw_boo_finalize", "mw_boo_is_initialised", "m
 #: the fields of mw_boo_plan / mw_boo_last, in order
 PLAN_FIELDS = ("boxes_per_chunk", "chunks", "small", "g1", "g2", "g3", "lds_bytes", "scratch_bytes_per_box", "boxes_per_workgroup")
 
-_dp = ctypes.POINTER(ctypes.c_double)
-_ip = ctypes.POINTER(ctypes.c_int)
-_lib = None
-_device = None                                  # the device this module initialised the library on
 
-
-def load_boo_library(path=BOO_LIB_PATH):
-    """dlopen libmw_boo.so.  Raises if it has not been built -- there is no fallback."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(path):
-        raise MwError(f"{path} not found: build it with `python -m mc_water_ls_mw_amd.build` (bond order has no CPU fallback)")
-    _share_hip_runtime_with_torch()
-    L = ctypes.CDLL(path)
-    L.mw_boo_last_error.restype = ctypes.c_char_p
+def _argtypes(L):
     for f in (L.mw_boo_compute, L.mw_boo_compute_device):
         f.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double,
                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    L.mw_boo_plan.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, _ip, ctypes.c_int]
-    _lib = L
-    return L
+    L.mw_boo_plan.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
 
 
-def _chk(L, rc):
-    if rc != 0:
-        raise MwError(L.mw_boo_last_error().decode())
+_dev = DevLib("boo", BOO_LIB_PATH, "bond order", PLAN_FIELDS, setup=_argtypes)
 
-
-def _live(device=None):
-    """The library, initialised on ``device`` (0 by default) if nobody has.  ``device`` given and the library live on
-    another one: an error -- it serves one device, and pointers of another must not reach it."""
-    global _device
-    L = load_boo_library()
-    if not L.mw_boo_is_initialised():
-        _chk(L, L.mw_boo_init(int(device or 0)))
-        _device = int(device or 0)
-    elif device is not None and _device is not None and int(device) != _device:
-        raise MwError(f"libmw_boo.so is initialised on device {_device}, not on device {int(device)}: call boo_finalize() first")
-    return L
+load_boo_library = _dev.load                     # (path=BOO_LIB_PATH): dlopen libmw_boo.so; raises if it has not been built
+boo_finalize = _dev.finalize
+boo_last = _dev.last                             # the fields of boo_plan for the last call that launched (the grid is that of its first box)
 
 
 def boo_init(device=0):
     """Initialise the library on ``device`` (the compute functions do it on device 0 when nobody has)."""
-    return _live(device)
-
-
-def boo_finalize():
-    global _device
-    L = load_boo_library()
-    _chk(L, L.mw_boo_finalize())
-    _device = None
-
-
-def _fields(out):
-    d = dict(zip(PLAN_FIELDS, (int(v) for v in out)))
-    d["small"] = bool(d["small"])
-    return d
+    return _dev.live(device)
 
 
 def boo_plan(nwater, cell, rc_ang=3.5, nboxes=1):
     """{field: value} of PLAN_FIELDS: the launch rules of ``nboxes`` boxes of ``nwater`` molecules with the cell ``cell``
     [3, 3] (bohr) and the cutoff ``rc_ang`` (mw_boo_plan), no device needed."""
-    L = load_boo_library()
-    out = (ctypes.c_int * len(PLAN_FIELDS))()
+    L = _dev.load()
+    out = _dev.plan_out()
     cell = np.ascontiguousarray(cell, dtype=np.float64)
     if cell.shape != (3, 3):
         raise MwError(f"cell {cell.shape}: expected [3, 3]")
-    _chk(L, L.mw_boo_plan(int(nwater), cell.ctypes.data, float(rc_ang) / BOHR_TO_ANG, int(nboxes), out, len(out)))
-    return _fields(out)
-
-
-def boo_last():
-    """The same fields for the last call that launched (the grid is that of its first box)."""
-    L = load_boo_library()
-    out = (ctypes.c_int * len(PLAN_FIELDS))()
-    _chk(L, L.mw_boo_last(out, len(out)))
-    return _fields(out)
+    _dev.chk(L.mw_boo_plan(int(nwater), cell.ctypes.data, float(rc_ang) / BOHR_TO_ANG, int(nboxes), out, len(out)))
+    return _dev.fields(out)
 
 
 def boo_elapsed_ms():
     """(binning, pass 1, pass 2, summary) of the last call in milliseconds, from the library's event timers; the small
     geometry is one kernel, reported as pass 1."""
-    L = load_boo_library()
+    L = _dev.load()
     t = [ctypes.c_float(0.0) for _ in range(4)]
-    _chk(L, L.mw_boo_elapsed_ms(*[ctypes.byref(v) for v in t]))
+    _dev.chk(L.mw_boo_elapsed_ms(*[ctypes.byref(v) for v in t]))
     return tuple(v.value for v in t)
 
 
@@ -120,43 +72,30 @@ def bond_order(cells, pos, rc_ang=3.5, threshold=0.5):
     [nboxes, nwater, 3] in bohr: q = (q4, q6, qbar4, qbar6), nn = (neighbours within ``rc_ang``, connections with
     s_ij > ``threshold``), summary = (Q4, Q6, <qbar4>, <qbar6>).  One box may come without the leading axis, and then so
     do the results."""
-    cells = np.ascontiguousarray(cells, dtype=np.float64)
-    pos = np.ascontiguousarray(pos, dtype=np.float64)
-    single = cells.ndim == 2
-    if single:
-        cells, pos = cells[None], pos[None]
-    if cells.ndim != 3 or cells.shape[1:] != (3, 3) or pos.ndim != 3 or pos.shape[0] != cells.shape[0] or pos.shape[2] != 3:
-        raise MwError(f"cells {cells.shape} / pos {pos.shape}: expected [nboxes, 3, 3] and [nboxes, nwater, 3]")
-    L = _live()
+    cells, pos, single = host_boxes(cells, pos)
+    L = _dev.live()
     nb, n = pos.shape[0], pos.shape[1]
     q = np.zeros((nb, n, 4))
     nn = np.zeros((nb, n, 2), dtype=np.int32)
     summary = np.zeros((nb, 4))
-    _chk(L, L.mw_boo_compute(nb, n, cells.ctypes.data, pos.ctypes.data, float(rc_ang) / BOHR_TO_ANG, float(threshold),
-                             q.ctypes.data, nn.ctypes.data, summary.ctypes.data))
+    _dev.chk(L.mw_boo_compute(nb, n, cells.ctypes.data, pos.ctypes.data, float(rc_ang) / BOHR_TO_ANG, float(threshold),
+                              q.ctypes.data, nn.ctypes.data, summary.ctypes.data))
     return (q[0], nn[0], summary[0]) if single else (q, nn, summary)
 
 
 def bond_order_torch(cells_t, pos_t, rc_ang=3.5, threshold=0.5):
     """(q [nboxes, nwater, 4] float64, nn [nboxes, nwater, 2] int32, summary [nboxes, 4] float64) as tensors on the device
-    of the inputs: ``cells_t`` [nboxes, 3, 3] and ``pos_t`` [nboxes, nwater, 3], contiguous float64 device tensors
-    (mw_boo_compute_device)."""
+    of the inputs: ``cells_t`` [nboxes, 3, 3] and ``pos_t`` [nboxes, nwater, 3], contiguous float64 device tensors on the
+    device the library lives on (mw_boo_compute_device)."""
     import torch
-    for t, name in ((cells_t, "cells_t"), (pos_t, "pos_t")):
-        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
-            raise MwError(f"{name}: expected a contiguous float64 device tensor")
-    if cells_t.dim() != 3 or tuple(cells_t.shape[1:]) != (3, 3) or pos_t.dim() != 3 or pos_t.shape[0] != cells_t.shape[0] \
-            or pos_t.shape[2] != 3:
-        raise MwError("expected cells_t [nboxes, 3, 3] and pos_t [nboxes, nwater, 3]")
-    dev = pos_t.device
-    if cells_t.device != dev:
-        raise MwError("the two tensors must be on one device")
-    L = _live(dev.index or 0)                      # raises if the library lives on another device
+    dev = check_device_tensors((cells_t, torch.float64, "cells_t"), (pos_t, torch.float64, "pos_t"))
+    check_boxes(cells_t, pos_t)
+    L = _dev.live(dev.index or 0)                  # raises if the library lives on another device
     nb, n = pos_t.shape[0], pos_t.shape[1]
     q = torch.zeros((nb, n, 4), dtype=torch.float64, device=dev)
     nn = torch.zeros((nb, n, 2), dtype=torch.int32, device=dev)
     summary = torch.zeros((nb, 4), dtype=torch.float64, device=dev)
     torch.cuda.synchronize(dev)
-    _chk(L, L.mw_boo_compute_device(nb, n, cells_t.data_ptr(), pos_t.data_ptr(), float(rc_ang) / BOHR_TO_ANG, float(threshold),
-                                    q.data_ptr(), nn.data_ptr(), summary.data_ptr()))
+    _dev.chk(L.mw_boo_compute_device(nb, n, cells_t.data_ptr(), pos_t.data_ptr(), float(rc_ang) / BOHR_TO_ANG, float(threshold),
+                                     q.data_ptr(), nn.data_ptr(), summary.data_ptr()))
     return q, nn, summary

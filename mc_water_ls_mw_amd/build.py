@@ -1,12 +1,11 @@
-"""Build libmw_hip.so (the C-ABI engine), libmw_comms.so (the RCCL exchange layer for a Fortran host, include/mw_comms.h)
+"""Build libmw_hip.so (the C-ABI engine), libmw_comms.so (the RCCL exchange layer for a Fortran host, include/mw_comms.h),
 libmw_sk.so (the structure factor S(k), include/mw_sk.h) and libmw_boo.so (the Steinhardt bond-order parameters,
 include/mw_boo.h) in-tree with hipcc for gfx950.
 
     python -m mc_water_ls_mw_amd.build [--force]
 
-hipcc cross-compiles gfx950 without a GPU, so this also runs in the build
-container.  The .so stays inside the package directory (git-ignored, but it
-travels to the GPU box with the gpurun snapshot).
+Each library is one hipcc call (`_compile`), skipped when the library is newer than every file it depends on.  hipcc
+cross-compiles gfx950 without a GPU.  The libraries stay inside the package directory, git-ignored.
 """
 from __future__ import annotations
 
@@ -24,20 +23,18 @@ DEPS = SOURCES + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.end
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                "-fno-fast-math", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 
-
 COMMS_LIB = os.path.join(PKG, "libmw_comms.so")
 COMMS_SRC = os.path.join(CSRC, "mw_comms.hip")
 COMMS_DEPS = [COMMS_SRC, os.path.join(os.path.dirname(PKG), "include", "mw_comms.h")]
 
-
+LIB_HOST = os.path.join(CSRC, "mw_lib_host.h")       # the host layer libmw_sk.so and libmw_boo.so share; not a dependency of libmw_hip.so
 SK_LIB = os.path.join(PKG, "libmw_sk.so")
 SK_SRC = os.path.join(CSRC, "mw_sk.hip")
-SK_DEPS = [SK_SRC, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_sk.h")]
-
+SK_DEPS = [SK_SRC, LIB_HOST, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_sk.h")]
 
 BOO_LIB = os.path.join(PKG, "libmw_boo.so")
 BOO_SRC = os.path.join(CSRC, "mw_boo.hip")
-BOO_DEPS = [BOO_SRC, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_boo.h")]
+BOO_DEPS = [BOO_SRC, LIB_HOST, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_boo.h")]
 
 
 def hipcc_path():
@@ -48,64 +45,47 @@ def hipcc_path():
 
 
 def needs_build():
-    if not os.path.exists(LIB):
-        return True
-    t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(p) > t for p in DEPS)
+    return _stale(LIB, DEPS)
 
 
-def build(force=False, verbose=False, extra_flags=(), out=None):
-    """`out`: another file name for a variant of the library (diagnostic builds, A/B measurements with MW_HIP_LIB)."""
-    lib = out or LIB
-    if not force and out is None and not needs_build():
-        return LIB
-    if out is not None and not force and os.path.exists(out) and all(os.path.getmtime(p) <= os.path.getmtime(out) for p in DEPS):
-        return out
-    cmd = [hipcc_path(), *HIPCC_FLAGS, *extra_flags, "-o", lib, *SOURCES]
+def _stale(lib, deps):
+    return not os.path.exists(lib) or any(os.path.getmtime(p) > os.path.getmtime(lib) for p in deps)
+
+
+def _compile(lib, sources, deps, flags, link=(), force=False, verbose=False):
+    """hipcc `flags` -o `lib` `sources` `link`, unless `lib` is newer than every file of `deps`."""
+    if not force and not _stale(lib, deps):
+        return lib
+    cmd = [hipcc_path(), *flags, "-o", lib, *sources, *link]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
     return lib
 
 
+def build(force=False, verbose=False, extra_flags=(), out=None):
+    """`out`: another file name for a variant of the library (diagnostic builds, A/B measurements with MW_HIP_LIB)."""
+    return _compile(out or LIB, SOURCES, DEPS, [*HIPCC_FLAGS, *extra_flags], force=force, verbose=verbose)
+
+
 def build_comms(force=False, verbose=False):
     """libmw_comms.so: host code only (no kernels), linked against RCCL."""
-    if not force and os.path.exists(COMMS_LIB) and all(os.path.getmtime(p) <= os.path.getmtime(COMMS_LIB) for p in COMMS_DEPS):
-        return COMMS_LIB
-    cmd = [hipcc_path(), "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-o", COMMS_LIB, COMMS_SRC,
-           "-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib"]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    return COMMS_LIB
+    return _compile(COMMS_LIB, [COMMS_SRC], COMMS_DEPS, ["--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall"],
+                    ["-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib"], force, verbose)
 
 
 def build_sk(force=False, verbose=False):
     """libmw_sk.so: the structure-factor kernels and their C ABI, a translation unit of its own (libmw_hip.so's code object
     and symbols do not move with it)."""
-    if not force and os.path.exists(SK_LIB) and all(os.path.getmtime(p) <= os.path.getmtime(SK_LIB) for p in SK_DEPS):
-        return SK_LIB
-    cmd = [hipcc_path(), *HIPCC_FLAGS, "-o", SK_LIB, SK_SRC]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    return SK_LIB
+    return _compile(SK_LIB, [SK_SRC], SK_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
 
 
 def build_boo(force=False, verbose=False):
     """libmw_boo.so: the bond-order kernels and their C ABI, a translation unit of its own like libmw_sk.so."""
-    if not force and os.path.exists(BOO_LIB) and all(os.path.getmtime(p) <= os.path.getmtime(BOO_LIB) for p in BOO_DEPS):
-        return BOO_LIB
-    cmd = [hipcc_path(), *HIPCC_FLAGS, "-o", BOO_LIB, BOO_SRC]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    return BOO_LIB
+    return _compile(BOO_LIB, [BOO_SRC], BOO_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
 
 
 if __name__ == "__main__":
-    build(force="--force" in sys.argv, verbose=True)
-    print(LIB)
-    print(build_comms(force="--force" in sys.argv, verbose=True))
-    print(build_sk(force="--force" in sys.argv, verbose=True))
-    print(build_boo(force="--force" in sys.argv, verbose=True))
+    force = "--force" in sys.argv
+    for builder in (build, build_comms, build_sk, build_boo):
+        print(builder(force=force, verbose=True))

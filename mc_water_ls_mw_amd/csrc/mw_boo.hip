@@ -9,14 +9,12 @@
 
 #include "mw_common.hip.h"
 
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #pragma clang fp contract(off)
+
+#include "mw_lib_host.h"                       // after the pragma: its host arithmetic is uncontracted too
 
 namespace mwboo {
 
@@ -429,58 +427,11 @@ namespace {
 
 using namespace mwboo;
 
-char g_err[512] = "";
-
-int fail(const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return 1;
-}
-
-#define HIPOK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail("%s: %s", #call, hipGetErrorString(e_)); } while (0)
-
-constexpr size_t kDefaultBudget = (size_t)256 << 20;
-
-struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-};
-
-struct State {
-    bool live = false;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t budget = kDefaultBudget;
+struct State : Runtime<5> {
     Buf scratch, par, grid, pos, q, nn, summary;
-    bool have_last = false;
     int last[MW_BOO_PLAN_FIELDS] = {0};
     float ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 } g;
-
-// Makes the library's device current and puts the caller's back when the call is over.
-struct DeviceScope {
-    int prev = -1;
-    hipError_t enter(int device)
-    {
-        const hipError_t e = hipGetDevice(&prev);
-        if (e != hipSuccess) { prev = -1; return e; }
-        return prev == device ? hipSuccess : hipSetDevice(device);
-    }
-    ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-int reserve(Buf& b, size_t bytes)
-{
-    if (bytes <= b.cap) return 0;
-    if (b.p) { HIPOK(hipFree(b.p)); b.p = nullptr; b.cap = 0; }
-    HIPOK(hipMalloc(&b.p, bytes));
-    b.cap = bytes;
-    return 0;
-}
 
 size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
@@ -539,24 +490,6 @@ void plan_fields(const Plan& p, const int grid[3], int* f)
 {
     f[0] = p.bpc; f[1] = p.chunks; f[2] = p.small; f[3] = grid[0]; f[4] = grid[1]; f[5] = grid[2];
     f[6] = p.lds; f[7] = (int)p.per_box; f[8] = p.boxes_per_wg;
-}
-
-// H^-1 (row-major) of the cell c (c[3 k + a] = H[a][k]); false if det is 0 or not finite
-bool invert_cell(const double* c, double* I, double* det_out)
-{
-    double H[3][3], C[3][3];
-    for (int a = 0; a < 3; ++a) for (int k = 0; k < 3; ++k) H[a][k] = c[3 * k + a];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
-            C[i][j] = std::fma(H[i1][j1], H[i2][j2], -(H[i1][j2] * H[i2][j1]));
-        }
-    const double det = std::fma(H[0][0], C[0][0], std::fma(H[0][1], C[0][1], H[0][2] * C[0][2]));
-    *det_out = det;
-    if (!(det != 0.0) || !std::isfinite(det)) return false;
-    for (int a = 0; a < 3; ++a) for (int k = 0; k < 3; ++k) I[3 * a + k] = C[k][a] / det;
-    for (int e = 0; e < 9; ++e) if (!std::isfinite(I[e])) return false;
-    return true;
 }
 
 // w_k = |det| / |h_l x h_m|
@@ -619,11 +552,7 @@ int check_cells(const char* who, int nboxes, int n, const double* cells, double 
     return 0;
 }
 
-int check_live(const char* who)
-{
-    if (!g.live) return fail("%s: not initialised (call mw_boo_init first)", who);
-    return 0;
-}
+int check_live(const char* who) { return check_live(who, "mw_boo_init", g); }
 
 dim3 per_molecule(int n, int nb) { return dim3((unsigned)((n + kThreads - 1) / kThreads), (unsigned)nb); }
 
@@ -737,53 +666,11 @@ extern "C" {
 const char* mw_boo_last_error(void) { return g_err; }
 int mw_boo_is_initialised(void) { return g.live ? 1 : 0; }
 
-int mw_boo_init(int device)
-{
-    if (g.live) return fail("mw_boo_init: already initialised");
-    int ndev = 0;
-    const hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev < 1)
-        return fail("mw_boo_init: no HIP device available (%s); this library has no CPU fallback",
-                    e == hipSuccess ? "device count 0" : hipGetErrorString(e));
-    if (device < 0) device = 0;
-    if (device >= ndev) return fail("mw_boo_init: device = %d of %d", device, ndev);
-    size_t budget = kDefaultBudget;
-    const char* mb = getenv("MW_BOO_SCRATCH_MB");
-    if (mb && *mb) {
-        char* end = nullptr;
-        const long v = strtol(mb, &end, 10);
-        if (end == mb || *end || v < 1 || v > (1L << 20)) return fail("mw_boo_init: MW_BOO_SCRATCH_MB = '%s' is not a number of MiB in 1..%ld", mb, 1L << 20);
-        budget = (size_t)v << 20;
-    }
-    DeviceScope scope;
-    HIPOK(scope.enter(device));
-    HIPOK(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
-    for (auto& ev : g.ev) {
-        const hipError_t ee = hipEventCreate(&ev);
-        if (ee != hipSuccess) {                              // give back what was made before failing
-            for (auto& made : g.ev) if (made) { (void)hipEventDestroy(made); made = nullptr; }
-            (void)hipStreamDestroy(g.stream);
-            g.stream = nullptr;
-            return fail("mw_boo_init: hipEventCreate: %s", hipGetErrorString(ee));
-        }
-    }
-    g.device = device;
-    g.budget = budget;
-    g.have_last = false;
-    g.live = true;
-    return 0;
-}
+int mw_boo_init(int device) { return runtime_init("mw_boo_init", "MW_BOO_SCRATCH_MB", device, g); }
 
 int mw_boo_finalize(void)
 {
-    if (!g.live) return 0;
-    DeviceScope scope;
-    HIPOK(scope.enter(g.device));
-    HIPOK(hipStreamSynchronize(g.stream));
-    for (Buf* b : {&g.scratch, &g.par, &g.grid, &g.pos, &g.q, &g.nn, &g.summary})
-        if (b->p) HIPOK(hipFree(b->p));
-    for (auto& ev : g.ev) HIPOK(hipEventDestroy(ev));
-    HIPOK(hipStreamDestroy(g.stream));
+    if (runtime_finalize(g, {&g.scratch, &g.par, &g.grid, &g.pos, &g.q, &g.nn, &g.summary})) return 1;
     g = State{};
     return 0;
 }
@@ -834,7 +721,7 @@ int mw_boo_plan(int nwater, const double* cell, double rc, int nboxes, int* out,
     if (make_plan(who, nwater, nboxes, g.live ? g.budget : kDefaultBudget, p)) return 1;
     int f[MW_BOO_PLAN_FIELDS];
     plan_fields(p, grid.data(), f);
-    for (int k = 0; k < nout && k < MW_BOO_PLAN_FIELDS; ++k) out[k] = f[k];
+    copy_fields(f, MW_BOO_PLAN_FIELDS, out, nout);
     return 0;
 }
 
@@ -843,7 +730,7 @@ int mw_boo_last(int* out, int nout)
     if (check_live("mw_boo_last")) return 1;
     if (!out || nout < 1) return fail("mw_boo_last: out is NULL or nout < 1");
     if (!g.have_last) return fail("mw_boo_last: no call has launched yet");
-    for (int k = 0; k < nout && k < MW_BOO_PLAN_FIELDS; ++k) out[k] = g.last[k];
+    copy_fields(g.last, MW_BOO_PLAN_FIELDS, out, nout);
     return 0;
 }
 

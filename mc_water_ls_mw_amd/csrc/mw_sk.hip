@@ -8,14 +8,11 @@
 
 #include "mw_common.hip.h"
 
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #pragma clang fp contract(off)
+
+#include "mw_lib_host.h"                       // after the pragma: its host arithmetic is uncontracted too
 
 namespace mwsk {
 
@@ -167,46 +164,11 @@ namespace {
 
 using namespace mwsk;
 
-char g_err[512] = "";
-
-int fail(const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return 1;
-}
-
-#define HIPOK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail("%s: %s", #call, hipGetErrorString(e_)); } while (0)
-
-constexpr size_t kDefaultBudget = (size_t)256 << 20;
-
-struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-};
-
-struct State {
-    bool live = false;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    size_t budget = kDefaultBudget;
+struct State : Runtime<3> {
     Buf scratch, inv, pos, nvec, rho, S, Sall, mean;
-    bool have_last = false;
     int last[MW_SK_PLAN_FIELDS] = {0};
     float ms_phasors = 0.0f, ms_sums = 0.0f;
 } g;
-
-int reserve(Buf& b, size_t bytes)
-{
-    if (bytes <= b.cap) return 0;
-    if (b.p) { HIPOK(hipFree(b.p)); b.p = nullptr; b.cap = 0; }
-    HIPOK(hipMalloc(&b.p, bytes));
-    b.cap = bytes;
-    return 0;
-}
 
 struct Plan {
     int small, rows, tile, jtlog, stride, nseg, seglen, bpc, chunks;
@@ -268,24 +230,6 @@ int check_nvec(const char* who, int M, const int* nvec, int nmax[3])
     return 0;
 }
 
-// H^-1 (row-major) of the cell c (c[3 k + a] = H[a][k]); false if det is 0 or not finite
-bool invert_cell(const double* c, double* I, double* det_out)
-{
-    double H[3][3], C[3][3];
-    for (int a = 0; a < 3; ++a) for (int k = 0; k < 3; ++k) H[a][k] = c[3 * k + a];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
-            C[i][j] = std::fma(H[i1][j1], H[i2][j2], -(H[i1][j2] * H[i2][j1]));
-        }
-    const double det = std::fma(H[0][0], C[0][0], std::fma(H[0][1], C[0][1], H[0][2] * C[0][2]));
-    *det_out = det;
-    if (!(det != 0.0) || !std::isfinite(det)) return false;
-    for (int a = 0; a < 3; ++a) for (int k = 0; k < 3; ++k) I[3 * a + k] = C[k][a] / det;
-    for (int e = 0; e < 9; ++e) if (!std::isfinite(I[e])) return false;
-    return true;
-}
-
 int check_cells(const char* who, int nboxes, const double* cells, std::vector<double>& inv)
 {
     inv.resize(9 * (size_t)nboxes);
@@ -297,11 +241,7 @@ int check_cells(const char* who, int nboxes, const double* cells, std::vector<do
     return 0;
 }
 
-int check_live(const char* who)
-{
-    if (!g.live) return fail("%s: not initialised (call mw_sk_init first)", who);
-    return 0;
-}
+int check_live(const char* who) { return check_live(who, "mw_sk_init", g); }
 
 // The work of every entry, arguments already checked.  `inv` is on the host; pos, nvec and the outputs are device pointers
 // when `dev`, host pointers otherwise.  `keepS`: leave S of all boxes in g.Sall (for the mean) and copy nothing out.
@@ -310,7 +250,8 @@ int run(const char* who, int nboxes, int n, int M, const std::vector<double>& in
 {
     Plan p;
     if (make_plan(who, n, nmax, M, nboxes, g.budget, p)) return 1;
-    HIPOK(hipSetDevice(g.device));
+    DeviceScope scope;
+    HIPOK(scope.enter(g.device));
     if (reserve(g.scratch, p.per_box * (size_t)p.bpc)) return 1;
     if (reserve(g.inv, inv.size() * sizeof(double))) return 1;
     HIPOK(hipMemcpyAsync(g.inv.p, inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice, g.stream));
@@ -392,43 +333,11 @@ extern "C" {
 const char* mw_sk_last_error(void) { return g_err; }
 int mw_sk_is_initialised(void) { return g.live ? 1 : 0; }
 
-int mw_sk_init(int device)
-{
-    if (g.live) return fail("mw_sk_init: already initialised");
-    int ndev = 0;
-    const hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev < 1)
-        return fail("mw_sk_init: no HIP device available (%s); this library has no CPU fallback",
-                    e == hipSuccess ? "device count 0" : hipGetErrorString(e));
-    if (device < 0) device = 0;
-    if (device >= ndev) return fail("mw_sk_init: device = %d of %d", device, ndev);
-    size_t budget = kDefaultBudget;
-    const char* mb = getenv("MW_SK_SCRATCH_MB");
-    if (mb && *mb) {
-        char* end = nullptr;
-        const long v = strtol(mb, &end, 10);
-        if (end == mb || *end || v < 1 || v > (1L << 20)) return fail("mw_sk_init: MW_SK_SCRATCH_MB = '%s' is not a number of MiB in 1..%ld", mb, 1L << 20);
-        budget = (size_t)v << 20;
-    }
-    HIPOK(hipSetDevice(device));
-    HIPOK(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
-    for (auto& ev : g.ev) HIPOK(hipEventCreate(&ev));
-    g.device = device;
-    g.budget = budget;
-    g.have_last = false;
-    g.live = true;
-    return 0;
-}
+int mw_sk_init(int device) { return runtime_init("mw_sk_init", "MW_SK_SCRATCH_MB", device, g); }
 
 int mw_sk_finalize(void)
 {
-    if (!g.live) return 0;
-    HIPOK(hipSetDevice(g.device));
-    HIPOK(hipStreamSynchronize(g.stream));
-    for (Buf* b : {&g.scratch, &g.inv, &g.pos, &g.nvec, &g.rho, &g.S, &g.Sall, &g.mean})
-        if (b->p) HIPOK(hipFree(b->p));
-    for (auto& ev : g.ev) HIPOK(hipEventDestroy(ev));
-    HIPOK(hipStreamDestroy(g.stream));
+    if (runtime_finalize(g, {&g.scratch, &g.inv, &g.pos, &g.nvec, &g.rho, &g.S, &g.Sall, &g.mean})) return 1;
     g = State{};
     return 0;
 }
@@ -452,7 +361,8 @@ int mw_sk_compute_device(int nboxes, int nwater, const double* cells, const doub
     std::vector<double> inv;
     if (check_common(who, nboxes, nwater, cells, pos, M, nvec)) return 1;
     if (check_live(who)) return 1;
-    HIPOK(hipSetDevice(g.device));
+    DeviceScope scope;
+    HIPOK(scope.enter(g.device));
     HIPOK(hipDeviceSynchronize());                            // whoever made the inputs (another stream, PyTorch's) is done
     std::vector<double> h_cells(9 * (size_t)nboxes);
     std::vector<int> h_nvec(3 * (size_t)M);
@@ -474,6 +384,8 @@ int mw_sk_mean(int nboxes, int nwater, const double* cells, const double* pos, i
     if (check_nvec(who, M, nvec, nmax)) return 1;
     if (check_cells(who, nboxes, cells, inv)) return 1;
     if (check_live(who)) return 1;
+    DeviceScope scope;                                        // over run() and the mean pass after it
+    HIPOK(scope.enter(g.device));
     if (run(who, nboxes, nwater, M, inv, pos, nvec, nmax, false, nullptr, nullptr, true)) return 1;
     const size_t bytes = 8 * (size_t)M * ngroups;
     if (reserve(g.mean, bytes)) return 1;
@@ -498,7 +410,7 @@ int mw_sk_plan(int nwater, const int nmax[3], int M, int nboxes, int* out, int n
     if (make_plan(who, nwater, nmax, M, nboxes, g.live ? g.budget : kDefaultBudget, p)) return 1;
     int f[MW_SK_PLAN_FIELDS];
     plan_fields(p, f);
-    for (int k = 0; k < nout && k < MW_SK_PLAN_FIELDS; ++k) out[k] = f[k];
+    copy_fields(f, MW_SK_PLAN_FIELDS, out, nout);
     return 0;
 }
 
@@ -507,7 +419,7 @@ int mw_sk_last(int* out, int nout)
     if (check_live("mw_sk_last")) return 1;
     if (!out || nout < 1) return fail("mw_sk_last: out is NULL or nout < 1");
     if (!g.have_last) return fail("mw_sk_last: no call has launched yet");
-    for (int k = 0; k < nout && k < MW_SK_PLAN_FIELDS; ++k) out[k] = g.last[k];
+    copy_fields(g.last, MW_SK_PLAN_FIELDS, out, nout);
     return 0;
 }
 

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from .energy import MwError, _share_hip_runtime_with_torch
+from ._devlib import DevLib, MwError, check_boxes, check_device_tensors, host_boxes
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 SK_LIB_PATH = os.path.join(PKG, "libmw_sk.so")
@@ -31,73 +31,32 @@ PLAN_FIELDS = ("boxes_per_chunk", "chunks", "kvec_per_lane", "segments", "lds_by
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int)
-_lib = None
+_dev = DevLib("sk", SK_LIB_PATH, "S(k)", PLAN_FIELDS)
 
-
-def load_sk_library(path=SK_LIB_PATH):
-    """dlopen libmw_sk.so.  Raises if it has not been built -- there is no fallback."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(path):
-        raise MwError(f"{path} not found: build it with `python -m mc_water_ls_mw_amd.build` (S(k) has no CPU fallback)")
-    _share_hip_runtime_with_torch()
-    L = ctypes.CDLL(path)
-    L.mw_sk_last_error.restype = ctypes.c_char_p
-    _lib = L
-    return L
-
-
-def _chk(L, rc):
-    if rc != 0:
-        raise MwError(L.mw_sk_last_error().decode())
-
-
-def _live(device=0):
-    L = load_sk_library()
-    if not L.mw_sk_is_initialised():
-        _chk(L, L.mw_sk_init(int(device)))
-    return L
+load_sk_library = _dev.load                     # (path=SK_LIB_PATH): dlopen libmw_sk.so; raises if it has not been built
+sk_finalize = _dev.finalize
+sk_last = _dev.last                             # the fields of sk_plan for the last call that launched
 
 
 def sk_init(device=0):
     """Initialise the library on ``device`` (the compute functions do it on device 0 when nobody has)."""
-    return _live(device)
-
-
-def sk_finalize():
-    L = load_sk_library()
-    _chk(L, L.mw_sk_finalize())
-
-
-def _fields(out):
-    d = dict(zip(PLAN_FIELDS, (int(v) for v in out)))
-    d["small"] = bool(d["small"])
-    return d
+    return _dev.live(device)
 
 
 def sk_plan(nwater, nmax, M, nboxes=1):
     """{field: value} of PLAN_FIELDS: the launch rules of a call (mw_sk_plan), no device needed."""
-    L = load_sk_library()
-    out = (ctypes.c_int * len(PLAN_FIELDS))()
+    L = _dev.load()
+    out = _dev.plan_out()
     nm = (ctypes.c_int * 3)(*[int(v) for v in nmax])
-    _chk(L, L.mw_sk_plan(int(nwater), nm, int(M), int(nboxes), out, len(out)))
-    return _fields(out)
-
-
-def sk_last():
-    """The same fields for the last call that launched."""
-    L = load_sk_library()
-    out = (ctypes.c_int * len(PLAN_FIELDS))()
-    _chk(L, L.mw_sk_last(out, len(out)))
-    return _fields(out)
+    _dev.chk(L.mw_sk_plan(int(nwater), nm, int(M), int(nboxes), out, len(out)))
+    return _dev.fields(out)
 
 
 def sk_elapsed_ms():
     """(table pass, sums) of the last call in milliseconds, from the library's event timers."""
-    L = load_sk_library()
+    L = _dev.load()
     a, b = ctypes.c_float(0.0), ctypes.c_float(0.0)
-    _chk(L, L.mw_sk_elapsed_ms(ctypes.byref(a), ctypes.byref(b)))
+    _dev.chk(L.mw_sk_elapsed_ms(ctypes.byref(a), ctypes.byref(b)))
     return a.value, b.value
 
 
@@ -156,12 +115,7 @@ def sq_from_sk(S, klen, q_max_ang, nbins):
 
 # -- the device calls -------------------------------------------------------------------------
 def _arrays(cells, pos, nvec):
-    cells = np.ascontiguousarray(cells, dtype=np.float64)
-    pos = np.ascontiguousarray(pos, dtype=np.float64)
-    if cells.ndim == 2:
-        cells, pos = cells[None], pos[None]
-    if cells.ndim != 3 or cells.shape[1:] != (3, 3) or pos.ndim != 3 or pos.shape[0] != cells.shape[0] or pos.shape[2] != 3:
-        raise MwError(f"cells {cells.shape} / pos {pos.shape}: expected [nboxes, 3, 3] and [nboxes, nwater, 3]")
+    cells, pos, _ = host_boxes(cells, pos)
     nvec = np.ascontiguousarray(nvec, dtype=np.int32)
     if nvec.ndim != 2 or nvec.shape[1] != 3:
         raise MwError(f"nvec {nvec.shape}: expected [M, 3]")
@@ -172,12 +126,12 @@ def structure_factor(cells, pos, nvec, want_rho=False):
     """S [nboxes, M] of the boxes ``cells`` [nboxes, 3, 3] / ``pos`` [nboxes, nwater, 3] (bohr; one box may come without the
     leading axis) for the triples ``nvec`` [M, 3]; with ``want_rho`` also rho as a complex array [nboxes, M]."""
     cells, pos, nvec = _arrays(cells, pos, nvec)
-    L = _live()
+    L = _dev.live()
     nb, n, M = pos.shape[0], pos.shape[1], nvec.shape[0]
     S = np.zeros((nb, M))
     rho = np.zeros((nb, M, 2)) if want_rho else None
-    _chk(L, L.mw_sk_compute(nb, n, cells.ctypes.data_as(_dp), pos.ctypes.data_as(_dp), M, nvec.ctypes.data_as(_ip),
-                            None if rho is None else rho.ctypes.data_as(_dp), S.ctypes.data_as(_dp)))
+    _dev.chk(L.mw_sk_compute(nb, n, cells.ctypes.data_as(_dp), pos.ctypes.data_as(_dp), M, nvec.ctypes.data_as(_ip),
+                             None if rho is None else rho.ctypes.data_as(_dp), S.ctypes.data_as(_dp)))
     if want_rho:
         return S, rho[..., 0] + 1j * rho[..., 1]
     return S
@@ -187,33 +141,29 @@ def structure_factor_mean(cells, pos, nvec, ngroups):
     """S_mean [ngroups, M]: box w * ngroups + g is walker w's box of group g; the mean over the walkers, taken on the device
     in walker order (mw_sk_mean)."""
     cells, pos, nvec = _arrays(cells, pos, nvec)
-    L = _live()
+    L = _dev.live()
     nb, n, M = pos.shape[0], pos.shape[1], nvec.shape[0]
     out = np.zeros((max(int(ngroups), 0), M))
-    _chk(L, L.mw_sk_mean(nb, n, cells.ctypes.data_as(_dp), pos.ctypes.data_as(_dp), M, nvec.ctypes.data_as(_ip), int(ngroups),
-                         out.ctypes.data_as(_dp)))
+    _dev.chk(L.mw_sk_mean(nb, n, cells.ctypes.data_as(_dp), pos.ctypes.data_as(_dp), M, nvec.ctypes.data_as(_ip), int(ngroups),
+                          out.ctypes.data_as(_dp)))
     return out
 
 
 def structure_factor_torch(cells_t, pos_t, nvec_t):
     """(S [nboxes, M], rho [nboxes, M, 2]) as float64 tensors on the device of the inputs: ``cells_t`` [nboxes, 3, 3] and
-    ``pos_t`` [nboxes, nwater, 3] float64, ``nvec_t`` [M, 3] int32, contiguous device tensors (mw_sk_compute_device)."""
+    ``pos_t`` [nboxes, nwater, 3] float64, ``nvec_t`` [M, 3] int32, contiguous device tensors on the device the library
+    lives on (mw_sk_compute_device)."""
     import torch
-    for t, dt, name in ((cells_t, torch.float64, "cells_t"), (pos_t, torch.float64, "pos_t"), (nvec_t, torch.int32, "nvec_t")):
-        if not (t.is_cuda and t.dtype == dt and t.is_contiguous()):
-            raise MwError(f"{name}: expected a contiguous {dt} device tensor")
-    if cells_t.dim() != 3 or tuple(cells_t.shape[1:]) != (3, 3) or pos_t.dim() != 3 or pos_t.shape[0] != cells_t.shape[0] \
-            or pos_t.shape[2] != 3 or nvec_t.dim() != 2 or nvec_t.shape[1] != 3:
-        raise MwError("expected cells_t [nboxes, 3, 3], pos_t [nboxes, nwater, 3], nvec_t [M, 3]")
-    dev = pos_t.device
-    if cells_t.device != dev or nvec_t.device != dev:
-        raise MwError("the three tensors must be on one device")
-    L = _live(dev.index or 0)
+    dev = check_device_tensors((cells_t, torch.float64, "cells_t"), (pos_t, torch.float64, "pos_t"), (nvec_t, torch.int32, "nvec_t"))
+    check_boxes(cells_t, pos_t)
+    if nvec_t.dim() != 2 or nvec_t.shape[1] != 3:
+        raise MwError(f"nvec_t {tuple(nvec_t.shape)}: expected [M, 3]")
+    L = _dev.live(dev.index or 0)                  # raises if the library lives on another device
     nb, n, M = pos_t.shape[0], pos_t.shape[1], nvec_t.shape[0]
     S = torch.zeros((nb, M), dtype=torch.float64, device=dev)
     rho = torch.zeros((nb, M, 2), dtype=torch.float64, device=dev)
     torch.cuda.synchronize(dev)
-    _chk(L, L.mw_sk_compute_device(nb, n, ctypes.c_void_p(cells_t.data_ptr()), ctypes.c_void_p(pos_t.data_ptr()), M,
-                                   ctypes.c_void_p(nvec_t.data_ptr()), ctypes.c_void_p(rho.data_ptr()),
-                                   ctypes.c_void_p(S.data_ptr())))
+    _dev.chk(L.mw_sk_compute_device(nb, n, ctypes.c_void_p(cells_t.data_ptr()), ctypes.c_void_p(pos_t.data_ptr()), M,
+                                    ctypes.c_void_p(nvec_t.data_ptr()), ctypes.c_void_p(rho.data_ptr()),
+                                    ctypes.c_void_p(S.data_ptr())))
     return S, rho

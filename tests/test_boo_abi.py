@@ -42,6 +42,8 @@ def test_build_boo_compiles_for_gfx950():
     assert set(build.BOO_DEPS) >= {build.BOO_SRC, header} and all(os.path.exists(p) for p in build.BOO_DEPS)
     assert not any(p in build.DEPS for p in (build.BOO_SRC, header))             # libmw_hip.so does not move with it
     assert not any(p in build.SK_DEPS for p in (build.BOO_SRC, header))
+    shared = os.path.join(build.CSRC, "mw_lib_host.h")                          # the host layer both device libraries include
+    assert shared in build.SK_DEPS and shared in build.BOO_DEPS and shared not in build.DEPS
     assert os.path.basename(build.BOO_SRC) == "mw_boo.hip" and not any("boo" in f for f in os.listdir(build.CSRC) if f.endswith(".hip.h"))
 
 
