@@ -3,6 +3,7 @@
 //   mw_local_energy.hip.h   local_energy_wave, local_energy_wave_batched
 //   mw_move_scan.hip.h      move_energy_wave (WaveScratch, the stamp arrays)
 //   mw_move_moments.hip.h   move_energy_mom_wave, moments_commit
+//   mw_move_lanes.hip.h     move_energy_mom_lanes
 //   mw_local_server.hip.h   k_local_server
 // and the kernels k_move_energy, k_move_fallback and k_local_energy_single here (non-template kernels enter the code object in
 // the order of their definitions, which this file keeps).
@@ -13,6 +14,7 @@
 #include "mw_local_energy.hip.h"
 #include "mw_move_scan.hip.h"
 #include "mw_move_moments.hip.h"
+#include "mw_move_lanes.hip.h"
 
 namespace mw {
 
@@ -27,10 +29,8 @@ constexpr int kMoveChunk = 2048;   // requests per work item when the box is sta
 
 // (LAYOUT: SoA measures 1.4 % faster than the paired layout here -- 1288 vs 1306 us, tools/kbench -- now that the scan
 // reads one vector less per slot; the full-box kernel keeps the paired layout, where it is the faster one)
-// MOMPATH = true (with LDSPOS, SELFIMG = false): the moment path above; `mom` = the box moments [box][N][kMomStride] of the launch's boxes.
-#ifndef MW_MOVE_WHEN
-#define MW_MOVE_WHEN 1     // when the batched kernel asks for the moments (move_energy_mom_wave: WHEN); 0 and 2 measured: see DESIGN 3.2
-#endif
+// MOMPATH = true (with LDSPOS, SELFIMG = false): the moment path above, a lane pair per request (move_energy_mom_lanes); `mom` = the box
+// moments [box][N][kMomStride] of the launch's boxes.
 template <bool LDSPOS, int LAYOUT = kLayoutSoA, bool SELFIMG = true, bool MOMPATH = false>
 __global__ __launch_bounds__(1024)
 void k_move_energy(const double* __restrict__ pos, const double* __restrict__ ivect,
@@ -46,14 +46,9 @@ void k_move_energy(const double* __restrict__ pos, const double* __restrict__ iv
                    unsigned int* __restrict__ mtot = nullptr)   // MOMPATH: [work item][4] = {interactions old, slots old, interactions new, slots new} of the item's served requests
 {
     static_assert(!MOMPATH || (LDSPOS && !SELFIMG), "the moment path serves boxes staged in LDS whose cells hold no self-images");
-    __shared__ unsigned short s_ptab[MOMPATH ? kCap * (kCap - 1) / 2 : 1];           // pair p -> (a | b << 8), a < b
-    if constexpr (MOMPATH) {
-        for (int p = threadIdx.x; p < kCap * (kCap - 1) / 2; p += 1024) {
-            int a, b;
-            tri_pair(p, a, b, [](float x) { return sqrtf(x); });
-            s_ptab[p] = (unsigned short)(a | (b << 8));
-        }
-    }
+    // (the moment build's static LDS is what it was when a 552-byte pair table stood here: 512 of the bytes are the queue lengths of
+    //  the sixteen wavefronts' 32 requests)
+    __shared__ unsigned char s_qn[MOMPATH ? kCap * (kCap - 1) : 2];
     unsigned int acc[4] = {0u, 0u, 0u, 0u};
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int4 w = work[blockIdx.x];
@@ -135,46 +130,109 @@ void k_move_energy(const double* __restrict__ pos, const double* __restrict__ iv
             o_ = perm[(unsigned)m_];
         }
     };
-    int cur = wave;
-    int i, o; uint32_t e; double t;
-    fetch(cur, i, e, t, o);
-    while (cur < nreq) {
-        int nxt = 0;
-        if (lane == 0) nxt = __hip_atomic_fetch_add(&s_next, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        nxt = LDSPOS ? __builtin_amdgcn_readfirstlane(nxt) : nreq;
-        int i_nx, o_nx; uint32_t e_nx; double t_nx;
-        fetch(nxt, i_nx, e_nx, t_nx, o_nx);
-
-        const int m = w.y + cur;
-        double xo, yo, zo;
-        getpos(i, xo, yo, zo);
-        double xn = xo, yn = yo, zn = zo;
-        if (mode & 2) { xn = readlane_f64(t, 0); yn = readlane_f64(t, 1); zn = readlane_f64(t, 2); }
-
-        MoveRes r;
-        bool fast;
-        if constexpr (MOMPATH) fast = move_energy_mom_wave<false, 0, MW_MOVE_WHEN>(getpos, getiv, nnof, mom + (size_t)b * N * kMomStride, ws, s_ptab, i, nnof(i), e, xo, yo, zo, xn, yn, zn, lane, r, acc, nullptr, nullptr, nullptr, nullptr, count);
-        else fast = move_energy_wave<SELFIMG>(getpos, getiv, row, nnof, ws, niv, i, nnof(i), e, xo, yo, zo, xn, yn, zn, lane, r);
-        // (the next request's three values are taken HERE, ahead of the result stores: taken at the loop's end, the wait for them would
-        //  also wait for those stores to be acknowledged, once per request.  On the scan path this is where they are waited for; on
-        //  the moment path they have arrived with the moments and this only fixes the place)
-        asm volatile("" : "+v"(e_nx), "+v"(t_nx), "+v"(o_nx));
-        if (!fast) {
-            // a request the fused routine declines (a row longer than 32 entries, more than kCap in-range neighbours, a
-            // molecule that neighbours its own image -- never on ice) is left to k_move_fallback: with the plain routine
-            // inlined here its registers counted against this loop (37 scalar registers spilled to vector lanes, ~30
-            // vector instructions per request on moving them), and calling it out of line costs scratch (+8 % time)
-            if (lane == 0 && !quiet) {
-                const int k = atomicAdd(&declined[(mode >> 2) & 1], 1);
-                declined[2 + 2 * k] = m; declined[3 + 2 * k] = b;
+    if constexpr (MOMPATH) {
+        // THE MOMENT PATH (mw_move_lanes.hip.h): a wavefront serves GROUPS of 32 consecutive requests of the item, lanes 2r and 2r + 1
+        // request r of the group at the old and at the trial position; the ticket hands out groups, the first sixteen to the sixteen
+        // wavefronts.  What a request brings from global memory -- its slot in the caller's order, its trial position, the first four
+        // entries of its molecule's row -- each lane asks for itself with vector loads, for the NEXT group, before the current group's
+        // result stores: the stores wait for nothing, and the loads are in flight across them and the ticket.
+        uint32_t* wq = reinterpret_cast<uint32_t*>(ws);
+        unsigned char* qn = s_qn + wave * 32;
+        const double* MOM = mom + (size_t)b * N * kMomStride;
+        const int rq = lane >> 1, side = lane & 1;
+        const int ngrp = (nreq + 31) >> 5;
+        auto fetch = [&](int grp, int& i_, int& o_, double (&t_)[3], uint4& c_) {
+            i_ = 0; o_ = 0; t_[0] = t_[1] = t_[2] = 0.0; c_ = make_uint4(0u, 0u, 0u, 0u);
+            if (grp < ngrp) {
+                const int q = min(grp * 32 + rq, nreq - 1);       // (a lane past the item's end repeats its last request and serves nothing)
+                const unsigned m_ = (unsigned)(w.y + q);
+                i_ = simol[q];
+                c_ = *reinterpret_cast<const uint4*>(LM + (size_t)i_ * kRow);
+                if (mode & 2) { t_[0] = req_trial[3u * m_]; t_[1] = req_trial[3u * m_ + 1u]; t_[2] = req_trial[3u * m_ + 2u]; }
+                o_ = perm[m_];
             }
-        } else if (lane == 0) {
-            const size_t so = (size_t)o;
-            if constexpr (MOMPATH) { r.io = r.so = r.in_ = r.sn = 0u; }       // (the counts of served requests go to `mtot`, summed per work item)
-            if (mode & 1) { if (!quiet) e_old[so] = r.eo; if (count) { counts[4 * so] = r.io; counts[4 * so + 1] = r.so; } }
-            if (mode & 2) { if (!quiet) e_new[so] = r.en; if (count) { counts[4 * so + 2] = r.in_; counts[4 * so + 3] = r.sn; } }
+        };
+        int cur = wave;
+        int i, o; double t[3]; uint4 c4;
+        fetch(cur, i, o, t, c4);
+        while (cur < ngrp) {
+            int nxt = 0;
+            if (lane == 0) nxt = __hip_atomic_fetch_add(&s_next, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            nxt = __builtin_amdgcn_readfirstlane(nxt);
+            int i_nx, o_nx; double t_nx[3]; uint4 c_nx;
+            const int q = cur * 32 + rq;
+            const bool valid = q < nreq;
+            double px, py, pz;                                    // this lane's position: the old one, in the odd lane the trial one
+            getpos(i, px, py, pz);
+            if ((mode & 2) && side) { px = t[0]; py = t[1]; pz = t[2]; }
+            const int n_i = valid ? min(nnof(i), kRow) : 0;
+            double en = 0.0;
+            unsigned int ci = 0u, cs = 0u;
+            const bool served = move_energy_mom_lanes(getpos, getiv, nnof, LM + (size_t)i * kRow, MOM, wq, qn, i, n_i, c4,
+                                                      px, py, pz, lane, count, en, ci, cs);
+            // (the next group's loads leave HERE, behind the evaluation and ahead of the result stores: issued at the loop's top they
+            //  are thirteen registers held across the evaluation, which has none to spare -- and a group starts on memory once per
+            //  32 requests, with three other wavefronts of the SIMD to fill the wait)
+            fetch(nxt, i_nx, o_nx, t_nx, c_nx);
+            if (valid && !served) {
+                // (declined: more than kLaneQueue in-range neighbours, a triplet the 0.99 rule drops, a molecule that lists itself --
+                //  left to k_move_fallback like the requests the scan builds decline)
+                if (side == 0 && !quiet) {
+                    const int k = atomicAdd(&declined[(mode >> 2) & 1], 1);
+                    declined[2 + 2 * k] = w.y + q; declined[3 + 2 * k] = b;
+                }
+            } else if (valid) {
+                const size_t so = (size_t)o;
+                // (the counts of served requests go to `mtot`, summed per work item; scalar bases: a per-lane choice of pointer is two
+                //  more registers held from group to group)
+                if (side == 0 && (mode & 1)) { if (!quiet) e_old[so] = en; if (count) { counts[4 * so] = 0u; counts[4 * so + 1] = 0u; } }
+                if (side == 1 && (mode & 2)) { if (!quiet) e_new[so] = en; if (count) { counts[4 * so + 2] = 0u; counts[4 * so + 3] = 0u; } }
+                if (count) { acc[0] += ci; acc[1] += cs; }        // (this lane's side: sorted out below)
+            }
+            wave_fence();                                         // (the queues are the next group's)
+            cur = nxt; i = i_nx; o = o_nx; t[0] = t_nx[0]; t[1] = t_nx[1]; t[2] = t_nx[2]; c4 = c_nx;
         }
-        cur = nxt; i = i_nx; e = e_nx; t = t_nx; o = o_nx;
+    } else {
+        int cur = wave;
+        int i, o; uint32_t e; double t;
+        fetch(cur, i, e, t, o);
+        while (cur < nreq) {
+            int nxt = 0;
+            if (lane == 0) nxt = __hip_atomic_fetch_add(&s_next, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            nxt = LDSPOS ? __builtin_amdgcn_readfirstlane(nxt) : nreq;
+            int i_nx, o_nx; uint32_t e_nx; double t_nx;
+            fetch(nxt, i_nx, e_nx, t_nx, o_nx);
+
+            const int m = w.y + cur;
+            double xo, yo, zo;
+            getpos(i, xo, yo, zo);
+            double xn = xo, yn = yo, zn = zo;
+            if (mode & 2) { xn = readlane_f64(t, 0); yn = readlane_f64(t, 1); zn = readlane_f64(t, 2); }
+
+            MoveRes r;
+            const bool fast = move_energy_wave<SELFIMG>(getpos, getiv, row, nnof, ws, niv, i, nnof(i), e, xo, yo, zo, xn, yn, zn, lane, r);
+            // (the next request's three values are taken HERE, ahead of the result stores: taken at the loop's end, the wait for them would
+            //  also wait for those stores to be acknowledged, once per request)
+            asm volatile("" : "+v"(e_nx), "+v"(t_nx), "+v"(o_nx));
+            if (!fast) {
+                // a request the fused routine declines (a row longer than 32 entries, more than kCap in-range neighbours, a
+                // molecule that neighbours its own image -- never on ice) is left to k_move_fallback: with the plain routine
+                // inlined here its registers counted against this loop (37 scalar registers spilled to vector lanes, ~30
+                // vector instructions per request on moving them), and calling it out of line costs scratch (+8 % time)
+                if (lane == 0 && !quiet) {
+                    const int k = atomicAdd(&declined[(mode >> 2) & 1], 1);
+                    declined[2 + 2 * k] = m; declined[3 + 2 * k] = b;
+                }
+            } else if (lane == 0) {
+                const size_t so = (size_t)o;
+                if (mode & 1) { if (!quiet) e_old[so] = r.eo; if (count) { counts[4 * so] = r.io; counts[4 * so + 1] = r.so; } }
+                if (mode & 2) { if (!quiet) e_new[so] = r.en; if (count) { counts[4 * so + 2] = r.in_; counts[4 * so + 3] = r.sn; } }
+            }
+            cur = nxt; i = i_nx; e = e_nx; t = t_nx; o = o_nx;
+        }
+    }
+    if constexpr (MOMPATH) if (count) {   // (the lane pairs kept their own side's two sums in acc[0], acc[1])
+        if (lane & 1) { acc[2] = acc[0]; acc[3] = acc[1]; acc[0] = acc[1] = 0u; }
     }
     if constexpr (MOMPATH) if (count) {   // the item's counts: lanes -> wavefront -> workgroup, ONE plain store per item (thousands of wavefronts adding to
         __shared__ unsigned int s_tot[16][4];                              // four global words serialise: +0.3 ms on a 0.9 ms launch)

@@ -1,0 +1,192 @@
+// mw_move_lanes.hip.h -- gfx950 (MI355X, CDNA4) device code of the mW energy engine:
+// the moment path of the batched single-move kernel with a LANE PAIR per trial move (move_energy_mom_lanes).
+#pragma once
+
+#include "mw_common.hip.h"
+#include "mw_full_energy.hip.h"
+#include "mw_move_scan.hip.h"
+
+namespace mw {
+
+// -------------------------------------------------------------------------------------
+// move_energy_mom_wave (mw_move_moments.hip.h) gives a request a whole wavefront, and a wave64 instruction costs the same with ten
+// live lanes as with 64: on thermal ice its expensive section runs with 15 of 64 lanes live.  Here a wavefront serves a GROUP of 32
+// requests: lanes 2r and 2r + 1 serve request r of the group at the old and at the trial position, in lockstep over the same entries,
+// the way the full-box kernel serves a molecule per lane (mw_full_energy.hip.h: atom_energy).
+//   phase 1  both lanes walk the n_i slots of i's row (up to kRow: no 32-slot limit), each against its own position, and park the
+//            entries in range of EITHER position, in row order, in the request's queue in LDS;
+//   phase 2  over the queue: the pair term and i's arm into the lane's own running sums (MomentSums: the j--i--k sum is
+//            1/2 [(|S2|^2 - Q) - 2 c0 (|S1|^2 - Q) + c0^2 (S0^2 - Q)] of them, no pair loop), and the i--j--k sum from j's moments less
+//            i's OLD arm, as in move_energy_mom_wave.
+// A lane's energy is the sum of its own terms in queue order: no cross-lane sum, so a request's bits depend on the request alone --
+// not on its group, its lane, its companions or whether counts are on.
+//
+// THE 0.99 RULE.  Neither sum can drop a term the reference drops (molint.F90:367-371), so a request that owns such a term is
+// DECLINED to k_move_fallback.  For a pair (a < b) of entries in range of one position P these are: b within the cutoff of a and
+// cos(theta_Pab) or cos(theta_Pba) >= 0.99 - 1e-9 (a third body in j's moments; the test of move_energy_mom_wave), and
+// cos(theta_aPb) >= 0.99 - 1e-9 (the j--i--k term the wave routine dropped itself).  All three imply |ab| < cutoff -- an angle
+// below 8.2 degrees between two arms shorter than the cutoff -- and |ab| does not depend on P: the two lanes of a pair SHARE the
+// pairs of the queue between them (lane `side` takes b = a + 1 + side, a + 3 + side, ...) and test |ab|^2 only; on ice it is almost
+// never below the cutoff.  When some lane finds such a pair, every lane takes its partner's b as well (DPP) and tests the angles of
+// its own pair and of its partner's at its OWN position, on squares (no square root).
+// Also declined: more than kLaneQueue entries in range of either position, and a molecule that lists itself.
+// -------------------------------------------------------------------------------------
+constexpr int kLaneQueue = 16;                                   // queue entries per request (thermal ice: 9.2 on average, never above 16)
+constexpr int kLaneQueueWords = 32 * kLaneQueue;                 // per wavefront: entry c of request r at word c * 32 + r (a trip reads 32 consecutive words)
+static_assert(kLaneQueueWords * sizeof(uint32_t) <= sizeof(WaveScratch), "the queues of a wavefront's 32 requests are overlaid on its WaveScratch");
+
+// the partner lane's value (lanes 2r <-> 2r + 1) and the even lane's value in both lanes, on the DPP network (every lane active)
+__device__ __forceinline__ int pair_swap_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, 0xb1, 0xf, 0xf, true); }   // quad_perm:[1,0,3,2]
+__device__ __forceinline__ int pair_even_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, 0xa0, 0xf, 0xf, true); }   // quad_perm:[0,0,2,2]
+__device__ __forceinline__ double pair_even_f64(double v) { return dpp_mov_f64<0xa0, 0xf>(v); }
+__device__ __forceinline__ double pair_swap_f64(double v) { return dpp_mov_f64<0xb1, 0xf>(v); }
+
+// One group: this lane's request is molecule `i` (row length n_i; 0 = no request in this lane), its row `rowp` = LM + i * kRow with
+// the first four entries already in `first`, and (px, py, pz) the position this lane evaluates: the old one in the even lane, the
+// trial one in the odd lane.  `wq` = the wavefront's queue words, `qn` = its 32 queue lengths (bytes).  Returns false when the
+// request is declined (the same answer in both lanes of a pair); else `E` = the local energy at this lane's position and, when
+// `count` (wave-uniform), `ci` / `cs` = its interactions and list slots.
+template <typename PosFn, typename IvFn, typename NnFn>
+__device__ __forceinline__ bool move_energy_mom_lanes(PosFn getpos, IvFn getiv, NnFn nnof, const uint32_t* __restrict__ rowp,
+                                                      const double* __restrict__ MOM, uint32_t* __restrict__ wq, unsigned char* __restrict__ qn,
+                                                      int i, int n_i, uint4 first, double px, double py, double pz,
+                                                      int lane, bool count, double& E, unsigned int& ci, unsigned int& cs)
+{
+    const int r = lane >> 1, side = lane & 1;
+    // r_j + ivect (molint.F90:269) and its squared distance from a position: ONE spelling for every in-range decision in here
+    auto image = [&](uint32_t e, double& qx, double& qy, double& qz) {
+        double xj, yj, zj, vx, vy, vz;
+        getpos((int)(e & kJMask), xj, yj, zj);
+        getiv((int)(e >> kJBits), vx, vy, vz);
+        qx = xj + vx; qy = yj + vy; qz = zj + vz;
+    };
+
+    // ---- phase 1: the scan -- four slots per load, one load ahead (the last one wraps to the row's start: never used) ----------
+    int cnt = 0;
+    bool self = false;
+    uint4 c4 = first;
+    for (int s0 = 0; __ballot(s0 < n_i) != 0ull; s0 += 4) {
+        const uint4 nx = *reinterpret_cast<const uint4*>(rowp + ((s0 + 4) & (kRow - 1)));
+        const uint32_t ent[4] = {c4.x, c4.y, c4.z, c4.w};
+#pragma unroll
+        for (int h = 0; h < 4; h += 2) {                         // two slots' gathers in flight together
+            double q[2][3];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) image(ent[h + u], q[u][0], q[u][1], q[u][2]);
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const bool has = s0 + h + u < n_i;
+                const bool mine = has && dist2(q[u][0] - px, q[u][1] - py, q[u][2] - pz) < kRcSq;   // :272,276
+                const int other = pair_swap_i32(mine ? 1 : 0);   // (unconditionally: every lane takes part in the exchange)
+                const bool inu = mine || other != 0;
+                self = self || (has && (int)(ent[h + u] & kJMask) == i);
+                if (inu) {                                       // (both lanes of the pair write the same word)
+                    if (cnt < kLaneQueue) wq[cnt * 32 + r] = ent[h + u];
+                    ++cnt;                                       // past the cap: counted, never stored
+                }
+            }
+        }
+        c4 = nx;
+    }
+    bool decl = self || cnt > kLaneQueue;
+    if (side == 0) qn[r] = (unsigned char)(cnt < kLaneQueue ? cnt : kLaneQueue);
+    wave_fence();
+    const int nq = (int)qn[r];
+
+    // ---- the 0.99 rule: the queue's pairs, shared between the two lanes --------------------------------------------------------
+    bool hard = false;
+    for (int a = 0; __ballot(a + 1 < nq) != 0ull; ++a) {
+        double ax, ay, az;
+        image(a + 1 < nq ? wq[a * 32 + r] : 0u, ax, ay, az);
+        for (int b0 = a + 1; __ballot(b0 < nq) != 0ull; b0 += 2) {
+            const int b = b0 + side;
+            const bool live = b < nq;
+            double bx, by, bz;
+            image(live ? wq[b * 32 + r] : 0u, bx, by, bz);
+            const double dx = bx - ax, dy = by - ay, dz = bz - az;                                 // a -> b
+            const double r2ab = dist2(dx, dy, dz);
+            const bool near = live && r2ab < kRcSq;
+            if (__ballot(near) != 0ull) {                        // wave-uniform: every lane is in here, and the exchange below is sound
+                const int near_o = pair_swap_i32(near ? 1 : 0);
+                const double ox = pair_swap_f64(bx), oy = pair_swap_f64(by), oz = pair_swap_f64(bz);   // the partner's b
+                constexpr double kC2 = (0.99 - 1e-9) * (0.99 - 1e-9);
+                auto angles = [&](bool on, double cx, double cy, double cz) {
+                    const double ex = cx - ax, ey = cy - ay, ez = cz - az;                             // a -> b
+                    const double r2e = dist2(ex, ey, ez);
+                    const double Ax = ax - px, Ay = ay - py, Az = az - pz, Bx = cx - px, By = cy - py, Bz = cz - pz;
+                    const double r2a = dist2(Ax, Ay, Az), r2b = dist2(Bx, By, Bz);
+                    if (on && r2a < kRcSq && r2b < kRcSq) {
+                        const double da = -(Ax * ex + Ay * ey + Az * ez), db = Bx * ex + By * ey + Bz * ez;   // (a->P).(a->b), (b->P).(b->a)
+                        const double dc = Ax * Bx + Ay * By + Az * Bz;                                    // (P->a).(P->b)
+                        hard = hard || (da > 0.0 && da * da >= kC2 * (r2a * r2e)) || (db > 0.0 && db * db >= kC2 * (r2b * r2e)) ||
+                               (dc > 0.0 && dc * dc >= kC2 * (r2a * r2b));
+                    }
+                };
+                angles(near, bx, by, bz);
+                angles(near_o != 0, ox, oy, oz);
+            }
+        }
+    }
+
+    // ---- phase 2: over the queue ------------------------------------------------------------------------------------------------
+    MomentSums ms;
+    double t3 = 0.0;
+    unsigned int packed = (unsigned int)n_i;
+    for (int k = 0; __ballot(k < nq) != 0ull; ++k) {
+        const bool live = k < nq;
+        const uint32_t e = live ? wq[k * 32 + r] : 0u;
+        const int j = (int)(e & kJMask);
+        double qx, qy, qz;
+        image(e, qx, qy, qz);
+        const double ax = qx - px, ay = qy - py, az = qz - pz;                                     // :272
+        const double r2 = dist2(ax, ay, az);
+        const bool in = live && r2 < kRcSq;                                                        // :276
+        // From here on NOTHING is conditional: an entry out of this lane's range goes through the same arithmetic with g = e1 = 0, which
+        // adds exact zeros to every sum (the lane's bits do not change), and the compiler has no branch to turn into selects that
+        // keep two copies of twenty running sums alive.  (Such a lane reads the moments of a molecule it has no use for: harmless.)
+        double M[10];
+        load_moments(MOM + (size_t)j * kMomStride, M);
+                                 // (used after the pair terms)
+        double rinv, e1, g;
+        pair_terms(in ? r2 : kRcSq, rinv, e1, g);                                                  // (out of range: finite values of no use)
+        e1 = in ? e1 : 0.0; g = in ? g : 0.0;
+        const double vx = -ax * rinv, vy = -ay * rinv, vz = -az * rinv;                            // unit vector j -> i, this position
+        // i's own term inside j's moments belongs to the OLD position (the one the full-box pass saw): the even lane's g (0 when j was
+        // out of range there) and unit vector
+        const double g_old = pair_even_f64(g), ux = pair_even_f64(vx), uy = pair_even_f64(vy), uz = pair_even_f64(vz);
+        ms.add(ax, ay, az, rinv, e1, g);                                                          // :294-297, and i's arm for the j--i--k sum
+        double S0 = M[0], S1x = M[1], S1y = M[2], S1z = M[3];
+        double Sxx = M[4], Syy = M[5], Sxy = M[6], Sxz = M[7], Syz = M[8];
+        double Szz = (S0 - Sxx) - Syy;                           // (trace of sum g u u^T = sum g)
+        {                            // one `m -= h * u` expression per component, as moments_arm<-1>
+            const double hx = g_old * ux, hy = g_old * uy, hz = g_old * uz;
+            S0 -= g_old; S1x -= hx; S1y -= hy; S1z -= hz;
+            Sxx -= hx * ux; Syy -= hy * uy; Szz -= hz * uz; Sxy -= hx * uy; Sxz -= hx * uz; Syz -= hy * uz;
+        }
+        const double wx = Sxx * vx + Sxy * vy + Sxz * vz, wy = Sxy * vx + Syy * vy + Syz * vz, wz = Sxz * vx + Syz * vy + Szz * vz;
+        const double quad = vx * wx + vy * wy + vz * wz, lin = vx * S1x + vy * S1y + vz * S1z;
+        t3 += g * ((quad - 2.0 * kCos0 * lin) + kCos0 * kCos0 * S0);                                   // :324-343,385-387 summed over k
+        if (count) {                 // one word: in-range neighbours << 27 | their other neighbours << 14 | their rows' slots (<= 16, 16 x 64, 17 x 64)
+            const bool in_old = pair_even_i32(in ? 1 : 0) != 0;
+            packed += in ? (1u << 27) + (((unsigned int)(M[9] + 0.5) - (in_old ? 1u : 0u)) << 14) + (unsigned int)nnof(j) : 0u;
+        }
+    }
+    {   // the j--i--k sum (:302-318) from the lane's own sums, as MomentSums::finish
+#pragma clang fp contract(off)
+        const double D2 = dist2(ms.Sxx, ms.Syy, ms.Szz), O2 = dist2(ms.Sxy, ms.Sxz, ms.Syz);
+        const double F2 = __builtin_fma(2.0, O2, D2);
+        const double F1 = dist2(ms.S1x, ms.S1y, ms.S1z);
+        const double A = F2 - ms.Q, B = F1 - ms.Q, C = __builtin_fma(ms.S0, ms.S0, -ms.Q);
+        const double T = 0.5 * __builtin_fma(kCos0 * kCos0, C, __builtin_fma(-2.0 * kCos0, B, A));
+        E = __builtin_fma(kLamEps, t3 + T, ms.e2);                                                 // :397
+    }
+    // (every pair of the lane's in-range neighbours contributes a j--i--k triplet: anything else was declined)
+    const unsigned int nin = packed >> 27;
+    ci = nin + nin * (nin - 1u) / 2u + ((packed >> 14) & 0x1fffu);
+    cs = packed & 0x3fffu;
+    decl = decl || hard;
+    const int decl_other = pair_swap_i32(decl ? 1 : 0);
+    return !(decl || decl_other != 0);
+}
+
+}  // namespace mw
