@@ -178,6 +178,7 @@ struct Ctx {
     int mcnt_state = kCountsThere;     // There: d_mcnt / d_mtot hold them; Pending: to be made on demand; Dropped: a pending launch's requests,
                                        // positions, cells or lists have changed since -- they cannot be made any more
     int mcnt_passes = 0;               // on-demand count passes launched since mw_init
+    bool move_sort = true;             // MW_MOVE_SORT != 0 at mw_moves_upload: the moment path sorts an item's requests by in-range neighbours
     bool move_counts_eager = false;    // MW_MOVE_COUNTS=eager at mw_init: the launch itself counts, as it used to
     int move_moments = -1;             // MW_MOVE_MOMENTS at mw_init: -1 unset (the request-count rule), 0 scanning path, 1 moment path where admitted
     int mchunk = 16;                 // requests per work item of the uploaded batch
@@ -251,6 +252,8 @@ size_t move_lds_bytes(int N, int ivcap, int chunk)
 {
     return kMoveScratch + mw::lds_vec_bytes((size_t)ivcap) + mw::lds_vec_bytes((size_t)N) + (((size_t)N + 7) & ~(size_t)7) + (size_t)chunk * sizeof(int);
 }
+// (the moment path packs a molecule's index into kKeyMolBits bits of a request's key: every N that fits pays 25 bytes a molecule)
+static_assert((size_t)kLdsBudget / 25 < ((size_t)1 << mw::kKeyMolBits), "a staged box's molecules fit the key of mw_move_energy.hip.h");
 bool lds_fits_move(int N, int ivcap)
 {
     return move_lds_bytes(N, ivcap, mw::kMoveChunk) <= (size_t)kLdsBudget;

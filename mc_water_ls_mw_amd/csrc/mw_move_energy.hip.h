@@ -24,8 +24,22 @@ namespace mw {
 //   mode bit 0: write e_old (mirrored positions), bit 1: write e_new (trial position), bit 2: the declined list's count word
 //   MOMPATH only -- bit 3: count (the interactions and slots of the served requests, summed per item into `mtot`, and the zero words
 //   of `counts`: without it the launch computes and writes nothing of them), bit 4: no energy output (nothing written to e_old or
-//   e_new, nothing appended to `declined`: the pass that counts on demand, mw_moves_counts)
+//   e_new, nothing appended to `declined`: the pass that counts on demand, mw_moves_counts), bit 5: sort the item's requests by
+//   their number of in-range neighbours before evaluating them (below; MW_MOVE_SORT=0 clears it)
 constexpr int kMoveChunk = 2048;   // requests per work item when the box is staged in LDS
+
+// MOMPATH keeps an item's requests in LDS as 32-bit KEYS: molecule | request index in the item << 13 | nq << 24, nq = the entries
+// of the molecule's row in range of the old or the trial position -- what phase 1 of move_energy_mom_lanes queues -- or kKeyNqOver
+// for a request that routine declines at once (more than kLaneQueue of them, or a molecule that lists itself).
+constexpr int kKeyMolBits = 13, kKeyReqBits = 11, kKeyNqBits = 5;          // (molecules: N <= 4372 where the box is staged, mw_host_ctx.hip.h)
+constexpr int kKeyReqShift = kKeyMolBits, kKeyNqShift = kKeyMolBits + kKeyReqBits;
+constexpr uint32_t kKeyMolMask = (1u << kKeyMolBits) - 1u, kKeyReqMask = (1u << kKeyReqBits) - 1u;
+constexpr int kKeyNqOver = kLaneQueue + 1;
+constexpr int kSortBins = kKeyNqOver + 1;                                  // nq = 0 .. kLaneQueue, and kKeyNqOver
+constexpr int kSortChunks = kMoveChunk / 64;                               // a wavefront ranks 64 keys at a time
+static_assert(kMoveChunk <= (1 << kKeyReqBits) && kKeyNqOver < (1 << kKeyNqBits) && kKeyNqShift + kKeyNqBits <= 32, "the key's fields");
+static_assert(kSortChunks == 2 * 16, "two rounds of the sixteen wavefronts rank an item's keys: chunks v and v + 16 in wavefront v");
+static_assert((kSortChunks + 1) * kSortBins * sizeof(uint32_t) <= 16 * sizeof(WaveScratch), "the sort's tables are overlaid on the idle queues");
 
 // (LAYOUT: SoA measures 1.4 % faster than the paired layout here -- 1288 vs 1306 us, tools/kbench -- now that the scan
 // reads one vector less per slot; the full-box kernel keeps the paired layout, where it is the faster one)
@@ -88,7 +102,10 @@ void k_move_energy(const double* __restrict__ pos, const double* __restrict__ iv
 #pragma unroll
             for (int k = 0; k < kB; ++k) { const int t = base + tid + k * 1024; v[k] = req_imol[w.y + (t < nreq ? t : nreq - 1)]; }
 #pragma unroll
-            for (int k = 0; k < kB; ++k) { const int t = base + tid + k * 1024; if (t < nreq) simol[t] = v[k]; }
+            for (int k = 0; k < kB; ++k) {                       // (MOMPATH: as keys, nq = 0)
+                const int t = base + tid + k * 1024;
+                if (t < nreq) simol[t] = MOMPATH ? (int)((uint32_t)v[k] | (uint32_t)t << kKeyReqShift) : v[k];
+            }
         }
         stage_vecs<LAYOUT, 1024>(spos, P, N, N, tid);
         if (tid == 0) s_next = 16;
@@ -131,22 +148,122 @@ void k_move_energy(const double* __restrict__ pos, const double* __restrict__ iv
         }
     };
     if constexpr (MOMPATH) {
-        // THE MOMENT PATH (mw_move_lanes.hip.h): a wavefront serves GROUPS of 32 consecutive requests of the item, lanes 2r and 2r + 1
-        // request r of the group at the old and at the trial position; the ticket hands out groups, the first sixteen to the sixteen
-        // wavefronts.  What a request brings from global memory -- its slot in the caller's order, its trial position, the first four
-        // entries of its molecule's row -- each lane asks for itself with vector loads, for the NEXT group, before the current group's
-        // result stores: the stores wait for nothing, and the loads are in flight across them and the ticket.
+        // THE MOMENT PATH (mw_move_lanes.hip.h): a wavefront serves GROUPS of 32 requests of the item, lanes 2r and 2r + 1 request r of
+        // the group at the old and at the trial position; the ticket hands out groups, the first sixteen to the sixteen wavefronts.
+        //
+        // WHICH 32.  The loops of the 0.99 rule and of phase 2 run for the longest queue among a group's requests, and on thermal ice a
+        // request queues 4 to 15 entries (9.2 on average): 32 consecutive requests hold a 13 or 14 nearly every time.  So an item of
+        // more than one group (mode bit 5) first COUNTS -- every wavefront runs phase 1's scan over its share of the groups, storing
+        // nothing, and writes each request's nq into its key -- then SORTS its keys by nq, longest first, stable in the request index
+        // (a counting sort over kSortBins bins; its tables lie on the queues, idle until then; four workgroup barriers per item, none
+        // in the loop below), and a lane takes its request from the sorted table: the ticket hands out the longest groups first, so the
+        // item ends on its cheapest.  Requests of nq = kKeyNqOver sort behind all others, are appended to the declined list here and are
+        // left out of the groups.  A request's bits are its own (mw_move_lanes.hip.h), so none of this changes a result.
+        // (Cheaper keys do not separate the requests -- bench walkers 0-2, phase-2 / pair-pass trips per item of 2048: 812 / 2577 as
+        //  uploaded, 594 / 1424 by nq; 782 / 2400 by the old position's in-range count, 809 / 2558 by row length, 751 / 2248 by a
+        //  bound from the displacement.)
+        //
+        // What a request brings from global memory -- its slot in the caller's order, its trial position, the first four entries of its
+        // molecule's row -- each lane asks for itself with vector loads, for the NEXT group, before the current group's result stores:
+        // the stores wait for nothing, and the loads are in flight across them and the ticket.  The count pass asks one group ahead too.
         uint32_t* wq = reinterpret_cast<uint32_t*>(ws);
         unsigned char* qn = s_qn + wave * 32;
         const double* MOM = mom + (size_t)b * N * kMomStride;
         const int rq = lane >> 1, side = lane & 1;
-        const int ngrp = (nreq + 31) >> 5;
+        uint32_t* skey = reinterpret_cast<uint32_t*>(simol);
+        int nserve = nreq;                                        // the requests the groups hold: the first `nserve` keys
+        if ((mode & 32) && nreq > 32) {
+            // ---- count: wavefront v takes groups v, v + 16, ... of the item as uploaded; only it reads or writes their keys ----
+            const int ngrp_up = (nreq + 31) >> 5;
+            auto image = [&](uint32_t e, double& qx, double& qy, double& qz) { lanes_image(getpos, getiv, e, qx, qy, qz); };
+            auto cfetch = [&](int grp, uint32_t& k_, double (&t_)[3], uint4& c_) {
+                k_ = 0u; t_[0] = t_[1] = t_[2] = 0.0; c_ = make_uint4(0u, 0u, 0u, 0u);
+                const int q = grp * 32 + rq;
+                if (q < nreq) {                                   // (a lane past the item's end: molecule 0, no slots)
+                    const unsigned m_ = (unsigned)(w.y + q);
+                    k_ = skey[q];
+                    c_ = *reinterpret_cast<const uint4*>(LM + (size_t)(k_ & kKeyMolMask) * kRow);
+                    if (mode & 2) { t_[0] = req_trial[3u * m_]; t_[1] = req_trial[3u * m_ + 1u]; t_[2] = req_trial[3u * m_ + 2u]; }
+                }
+            };
+            uint32_t k; double t[3]; uint4 c4;
+            cfetch(wave, k, t, c4);
+            for (int grp = wave; grp < ngrp_up; grp += 16) {
+                uint32_t k_nx; double t_nx[3]; uint4 c_nx;
+                cfetch(grp + 16, k_nx, t_nx, c_nx);
+                const int q = grp * 32 + rq;
+                const int i = (int)(k & kKeyMolMask);
+                double px, py, pz;
+                getpos(i, px, py, pz);
+                if ((mode & 2) && side) { px = t[0]; py = t[1]; pz = t[2]; }
+                const int n_i = q < nreq ? min(nnof(i), kRow) : 0;
+                int cnt = 0;
+                bool self = false;
+                lanes_scan<false>(image, LM + (size_t)i * kRow, wq, rq, i, n_i, c4, px, py, pz, cnt, self);
+                if (q < nreq && side == 0) skey[q] = k | (uint32_t)(self || cnt > kLaneQueue ? kKeyNqOver : cnt) << kKeyNqShift;
+                k = k_nx; t[0] = t_nx[0]; t[1] = t_nx[1]; t[2] = t_nx[2]; c4 = c_nx;
+            }
+            __syncthreads();
+            // ---- sort: chunk ch = 64 consecutive keys, wavefront v ranks chunks v and v + 16 (only the item's `nch`: an item of up
+            //      to 1024 requests has one round, and nothing is done for chunks it does not have); tab[ch][bin] = the chunk's keys of that bin, then the
+            //      number of such keys in earlier chunks; tab[kSortChunks][bin] = where the bin starts in the sorted table ----
+            uint32_t* tab = reinterpret_cast<uint32_t*>(ws - wave);
+            const int nch = (nreq + 63) >> 6;
+            uint32_t key[2] = {0u, 0u};
+            int rank[2] = {0, 0};
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int ch = wave + 16 * h, q = ch * 64 + lane;
+                if (ch >= nch) continue;                          // (wave-uniform)
+                key[h] = q < nreq ? skey[q] : 0u;
+                const int bin = q < nreq ? (int)(key[h] >> kKeyNqShift) : -1;
+                unsigned int mine = 0u;
+#pragma nounroll
+                for (int bn = 0; bn < kSortBins; ++bn) {          // (rolled: unrolled, the masks of all bins are held at once, in registers the main loop then lacks)
+                    const unsigned long long m = __ballot(bin == bn);
+                    if (bin == bn) rank[h] = __popcll(m & ((1ull << lane) - 1ull));   // the same bin in lower lanes: earlier requests
+                    if (lane == bn) mine = (unsigned int)__popcll(m);
+                }
+                if (lane < kSortBins) tab[ch * kSortBins + lane] = mine;
+            }
+            __syncthreads();
+            if (wave == 0) {                                      // lane l < kSortBins: the bin at place l of the order kLaneQueue .. 0, kKeyNqOver
+                const int bin = lane <= kLaneQueue ? kLaneQueue - lane : kKeyNqOver;
+                unsigned int run = 0u;
+                if (lane < kSortBins) {
+#pragma unroll
+                    for (int ch = 0; ch < kSortChunks; ++ch)
+                        if (ch < nch) { const unsigned int c = tab[ch * kSortBins + bin]; tab[ch * kSortBins + bin] = run; run += c; }
+                }
+                unsigned int at = 0u;
+#pragma nounroll
+                for (int l = 0; l + 1 < kSortBins; ++l) { const unsigned int tl = (unsigned int)__builtin_amdgcn_readlane((int)run, l); if (lane > l) at += tl; }
+                if (lane < kSortBins) tab[kSortChunks * kSortBins + bin] = at;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int ch = wave + 16 * h;
+                if (ch * 64 + lane < nreq) {
+                    const int bin = (int)(key[h] >> kKeyNqShift);
+                    skey[tab[kSortChunks * kSortBins + bin] + tab[ch * kSortBins + bin] + (unsigned int)rank[h]] = key[h];
+                }
+            }
+            nserve = __builtin_amdgcn_readfirstlane((int)tab[kSortChunks * kSortBins + kKeyNqOver]);
+            __syncthreads();                                      // (the sorted keys stand, and the tables are queues again)
+            if (!quiet)
+                for (int p = nserve + tid; p < nreq; p += 1024) {
+                    const int k2 = atomicAdd(&declined[(mode >> 2) & 1], 1);
+                    declined[2 + 2 * k2] = w.y + (int)((skey[p] >> kKeyReqShift) & kKeyReqMask); declined[3 + 2 * k2] = b;
+                }
+        }
+        const int ngrp = (nserve + 31) >> 5;
         auto fetch = [&](int grp, int& i_, int& o_, double (&t_)[3], uint4& c_) {
             i_ = 0; o_ = 0; t_[0] = t_[1] = t_[2] = 0.0; c_ = make_uint4(0u, 0u, 0u, 0u);
             if (grp < ngrp) {
-                const int q = min(grp * 32 + rq, nreq - 1);       // (a lane past the item's end repeats its last request and serves nothing)
-                const unsigned m_ = (unsigned)(w.y + q);
-                i_ = simol[q];
+                const uint32_t k_ = skey[min(grp * 32 + rq, nserve - 1)];   // (a lane past the end repeats the last request and serves nothing)
+                const unsigned m_ = (unsigned)w.y + ((k_ >> kKeyReqShift) & kKeyReqMask);
+                i_ = (int)(k_ & kKeyMolMask);
                 c_ = *reinterpret_cast<const uint4*>(LM + (size_t)i_ * kRow);
                 if (mode & 2) { t_[0] = req_trial[3u * m_]; t_[1] = req_trial[3u * m_ + 1u]; t_[2] = req_trial[3u * m_ + 2u]; }
                 o_ = perm[m_];
@@ -160,8 +277,7 @@ void k_move_energy(const double* __restrict__ pos, const double* __restrict__ iv
             if (lane == 0) nxt = __hip_atomic_fetch_add(&s_next, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             nxt = __builtin_amdgcn_readfirstlane(nxt);
             int i_nx, o_nx; double t_nx[3]; uint4 c_nx;
-            const int q = cur * 32 + rq;
-            const bool valid = q < nreq;
+            const bool valid = cur * 32 + rq < nserve;
             double px, py, pz;                                    // this lane's position: the old one, in the odd lane the trial one
             getpos(i, px, py, pz);
             if ((mode & 2) && side) { px = t[0]; py = t[1]; pz = t[2]; }
@@ -177,9 +293,9 @@ void k_move_energy(const double* __restrict__ pos, const double* __restrict__ iv
             if (valid && !served) {
                 // (declined: more than kLaneQueue in-range neighbours, a triplet the 0.99 rule drops, a molecule that lists itself --
                 //  left to k_move_fallback like the requests the scan builds decline)
-                if (side == 0 && !quiet) {
+                if (side == 0 && !quiet) {                        // (its index in the item: from its key again, no register across the evaluation)
                     const int k = atomicAdd(&declined[(mode >> 2) & 1], 1);
-                    declined[2 + 2 * k] = w.y + q; declined[3 + 2 * k] = b;
+                    declined[2 + 2 * k] = w.y + (int)((skey[cur * 32 + rq] >> kKeyReqShift) & kKeyReqMask); declined[3 + 2 * k] = b;
                 }
             } else if (valid) {
                 const size_t so = (size_t)o;

@@ -41,29 +41,25 @@ __device__ __forceinline__ int pair_even_i32(int v) { return __builtin_amdgcn_up
 __device__ __forceinline__ double pair_even_f64(double v) { return dpp_mov_f64<0xa0, 0xf>(v); }
 __device__ __forceinline__ double pair_swap_f64(double v) { return dpp_mov_f64<0xb1, 0xf>(v); }
 
-// One group: this lane's request is molecule `i` (row length n_i; 0 = no request in this lane), its row `rowp` = LM + i * kRow with
-// the first four entries already in `first`, and (px, py, pz) the position this lane evaluates: the old one in the even lane, the
-// trial one in the odd lane.  `wq` = the wavefront's queue words, `qn` = its 32 queue lengths (bytes).  Returns false when the
-// request is declined (the same answer in both lanes of a pair); else `E` = the local energy at this lane's position and, when
-// `count` (wave-uniform), `ci` / `cs` = its interactions and list slots.
-template <typename PosFn, typename IvFn, typename NnFn>
-__device__ __forceinline__ bool move_energy_mom_lanes(PosFn getpos, IvFn getiv, NnFn nnof, const uint32_t* __restrict__ rowp,
-                                                      const double* __restrict__ MOM, uint32_t* __restrict__ wq, unsigned char* __restrict__ qn,
-                                                      int i, int n_i, uint4 first, double px, double py, double pz,
-                                                      int lane, bool count, double& E, unsigned int& ci, unsigned int& cs)
+// r_j + ivect (molint.F90:269) of a row entry: ONE spelling for every in-range decision of the lane-pair routines
+template <typename PosFn, typename IvFn>
+__device__ __forceinline__ void lanes_image(PosFn getpos, IvFn getiv, uint32_t e, double& qx, double& qy, double& qz)
 {
-    const int r = lane >> 1, side = lane & 1;
-    // r_j + ivect (molint.F90:269) and its squared distance from a position: ONE spelling for every in-range decision in here
-    auto image = [&](uint32_t e, double& qx, double& qy, double& qz) {
-        double xj, yj, zj, vx, vy, vz;
-        getpos((int)(e & kJMask), xj, yj, zj);
-        getiv((int)(e >> kJBits), vx, vy, vz);
-        qx = xj + vx; qy = yj + vy; qz = zj + vz;
-    };
+    double xj, yj, zj, vx, vy, vz;
+    getpos((int)(e & kJMask), xj, yj, zj);
+    getiv((int)(e >> kJBits), vx, vy, vz);
+    qx = xj + vx; qy = yj + vy; qz = zj + vz;
+}
 
-    // ---- phase 1: the scan -- four slots per load, one load ahead (the last one wraps to the row's start: never used) ----------
-    int cnt = 0;
-    bool self = false;
+// THE SCAN of a lane pair over the n_i slots of molecule i's row `rowp` (its first four entries already in `first`), each lane
+// against its own position (px, py, pz): four slots per load, one load ahead (the last one wraps to the row's start: never used).
+// `cnt` = the entries in range of EITHER position, `self` = the row names i itself.  STORE: the first kLaneQueue of them are parked
+// in the request's queue, in row order (phase 1 of move_energy_mom_lanes); without it nothing is written (the count pass of
+// k_move_energy, which sorts an item's requests by `cnt` before any of them is evaluated).  The loop is wave-uniform.
+template <bool STORE, typename ImageFn>
+__device__ __forceinline__ void lanes_scan(ImageFn image, const uint32_t* __restrict__ rowp, uint32_t* __restrict__ wq, int r,
+                                           int i, int n_i, uint4 first, double px, double py, double pz, int& cnt, bool& self)
+{
     uint4 c4 = first;
     for (int s0 = 0; __ballot(s0 < n_i) != 0ull; s0 += 4) {
         const uint4 nx = *reinterpret_cast<const uint4*>(rowp + ((s0 + 4) & (kRow - 1)));
@@ -81,13 +77,33 @@ __device__ __forceinline__ bool move_energy_mom_lanes(PosFn getpos, IvFn getiv, 
                 const bool inu = mine || other != 0;
                 self = self || (has && (int)(ent[h + u] & kJMask) == i);
                 if (inu) {                                       // (both lanes of the pair write the same word)
-                    if (cnt < kLaneQueue) wq[cnt * 32 + r] = ent[h + u];
+                    if constexpr (STORE) { if (cnt < kLaneQueue) wq[cnt * 32 + r] = ent[h + u]; }
                     ++cnt;                                       // past the cap: counted, never stored
                 }
             }
         }
         c4 = nx;
     }
+}
+
+// One group: this lane's request is molecule `i` (row length n_i; 0 = no request in this lane), its row `rowp` = LM + i * kRow with
+// the first four entries already in `first`, and (px, py, pz) the position this lane evaluates: the old one in the even lane, the
+// trial one in the odd lane.  `wq` = the wavefront's queue words, `qn` = its 32 queue lengths (bytes).  Returns false when the
+// request is declined (the same answer in both lanes of a pair); else `E` = the local energy at this lane's position and, when
+// `count` (wave-uniform), `ci` / `cs` = its interactions and list slots.
+template <typename PosFn, typename IvFn, typename NnFn>
+__device__ __forceinline__ bool move_energy_mom_lanes(PosFn getpos, IvFn getiv, NnFn nnof, const uint32_t* __restrict__ rowp,
+                                                      const double* __restrict__ MOM, uint32_t* __restrict__ wq, unsigned char* __restrict__ qn,
+                                                      int i, int n_i, uint4 first, double px, double py, double pz,
+                                                      int lane, bool count, double& E, unsigned int& ci, unsigned int& cs)
+{
+    const int r = lane >> 1, side = lane & 1;
+    auto image = [&](uint32_t e, double& qx, double& qy, double& qz) { lanes_image(getpos, getiv, e, qx, qy, qz); };
+
+    // ---- phase 1: the scan, parking the entries in range of either position in the queue -----------------------------------------
+    int cnt = 0;
+    bool self = false;
+    lanes_scan<true>(image, rowp, wq, r, i, n_i, first, px, py, pz, cnt, self);
     bool decl = self || cnt > kLaneQueue;
     if (side == 0) qn[r] = (unsigned char)(cnt < kLaneQueue ? cnt : kLaneQueue);
     wave_fence();
