@@ -1,6 +1,7 @@
 """Build libmw_hip.so (the C-ABI engine), libmw_comms.so (the RCCL exchange layer for a Fortran host, include/mw_comms.h),
-libmw_sk.so (the structure factor S(k), include/mw_sk.h) and libmw_boo.so (the Steinhardt bond-order parameters,
-include/mw_boo.h) in-tree with hipcc for gfx950.
+libmw_sk.so (the structure factor S(k), include/mw_sk.h), libmw_boo.so (the Steinhardt bond-order parameters,
+include/mw_boo.h) and libmw_tet.so (tetrahedral order, d5 and LSI from the sorted nearest neighbours, include/mw_tet.h)
+in-tree with hipcc for gfx950.
 
     python -m mc_water_ls_mw_amd.build [--force]
 
@@ -27,7 +28,7 @@ COMMS_LIB = os.path.join(PKG, "libmw_comms.so")
 COMMS_SRC = os.path.join(CSRC, "mw_comms.hip")
 COMMS_DEPS = [COMMS_SRC, os.path.join(os.path.dirname(PKG), "include", "mw_comms.h")]
 
-LIB_HOST = os.path.join(CSRC, "mw_lib_host.h")       # the host layer libmw_sk.so and libmw_boo.so share; not a dependency of libmw_hip.so
+LIB_HOST = os.path.join(CSRC, "mw_lib_host.h")       # the host layer libmw_sk.so, libmw_boo.so and libmw_tet.so share; not a dependency of libmw_hip.so
 SK_LIB = os.path.join(PKG, "libmw_sk.so")
 SK_SRC = os.path.join(CSRC, "mw_sk.hip")
 SK_DEPS = [SK_SRC, LIB_HOST, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_sk.h")]
@@ -35,6 +36,10 @@ SK_DEPS = [SK_SRC, LIB_HOST, os.path.join(CSRC, "mw_common.hip.h"), os.path.join
 BOO_LIB = os.path.join(PKG, "libmw_boo.so")
 BOO_SRC = os.path.join(CSRC, "mw_boo.hip")
 BOO_DEPS = [BOO_SRC, LIB_HOST, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_boo.h")]
+
+TET_LIB = os.path.join(PKG, "libmw_tet.so")
+TET_SRC = os.path.join(CSRC, "mw_tet.hip")
+TET_DEPS = [TET_SRC, LIB_HOST, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_tet.h")]
 
 
 def hipcc_path():
@@ -85,7 +90,12 @@ def build_boo(force=False, verbose=False):
     return _compile(BOO_LIB, [BOO_SRC], BOO_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
 
 
+def build_tet(force=False, verbose=False):
+    """libmw_tet.so: the nearest-neighbour selection kernels and their C ABI, a translation unit of its own like libmw_boo.so."""
+    return _compile(TET_LIB, [TET_SRC], TET_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
+
+
 if __name__ == "__main__":
     force = "--force" in sys.argv
-    for builder in (build, build_comms, build_sk, build_boo):
+    for builder in (build, build_comms, build_sk, build_boo, build_tet):
         print(builder(force=force, verbose=True))

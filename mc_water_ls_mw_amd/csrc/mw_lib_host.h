@@ -1,4 +1,4 @@
-// The host layer the stand-alone device libraries share (libmw_sk.so, libmw_boo.so): the error buffer, growing device buffers,
+// The host layer the stand-alone device libraries share (libmw_sk.so, libmw_boo.so, libmw_tet.so): the error buffer, growing device buffers,
 // the device scope, the cell inverse and the life cycle of a library's stream, events and scratch budget.  Host code only, and
 // all of it with internal linkage: every library that includes this keeps an error buffer and a state of its own and exports
 // nothing from here.  (libmw_hip.so's host layer, mw_host_ctx.hip.h, is another contract and does not use this.)

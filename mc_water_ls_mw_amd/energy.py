@@ -507,6 +507,19 @@ class EnergyModule:
         self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
         return bondorder.bond_order(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, rc_ang, threshold)
 
+    # -- tetrahedral order, d5 and LSI (libmw_tet.so, include/mw_tet.h; no counterpart in the reference) ------------
+    def tetrahedral_order(self, first_ils=1, count=None, r_search_ang=5.5, r_lsi_ang=3.7):
+        """(order [count, nwater, 4], near [count, nwater, 4], counts [count, nwater, 2], summary [count, 8]) of ``count``
+        boxes -- tetrahedral.tetrahedral_order -- from the positions the DEVICE holds and this module's hmatrix (after device
+        volume moves call ``WalkerFarm.sync_cells`` first).  The positions take one host hop (mw_download_positions_range)
+        on their way to libmw_tet.so, which shares nothing with the engine but the device."""
+        from . import tetrahedral
+        count = self.num_lattices - first_ils + 1 if count is None else count
+        self._ils(first_ils), self._ils(first_ils + count - 1)
+        pos = np.zeros((count, self.nwater, 3))
+        self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
+        return tetrahedral.tetrahedral_order(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, r_search_ang, r_lsi_ang)
+
     def model_energy_counts(self, ils):
         p, t = ctypes.c_longlong(0), ctypes.c_longlong(0)
         self._chk(self.L.mw_model_energy_counts(ils, ctypes.byref(p), ctypes.byref(t)))

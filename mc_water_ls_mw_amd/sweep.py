@@ -355,6 +355,17 @@ class WalkerFarm:
         solid = (nn[:, :, 1] >= 3).sum(axis=1) / float(self.em.nwater)
         return summary.reshape(self.nwalkers, self.nlat, 4), solid.reshape(self.nwalkers, self.nlat)
 
+    def tetrahedral_order(self, r_search_ang=5.5, r_lsi_ang=3.7):
+        """(summary [nwalkers, nlat, 8], tetrahedral [nwalkers, nlat]): the means of (q, s_k, d5, lsi) over the molecules
+        where each is defined and the numbers of those molecules (include/mw_tet.h) of every lattice of every walker, and
+        the fraction of its molecules with q > 0.9, from the positions and cells the device holds (the cells read back
+        through :meth:`sync_cells` first).  q reads out the three-body term of the model directly: a lattice that is still a
+        four-coordinated crystal keeps its mean q near 1."""
+        self.sync_cells()
+        order, _, _, summary = self.em.tetrahedral_order(1, self.em.num_lattices, r_search_ang, r_lsi_ang)
+        tetra = (order[:, :, 0] > 0.9).sum(axis=1) / float(self.em.nwater)        # (NaN > 0.9 is False)
+        return summary.reshape(self.nwalkers, self.nlat, 8), tetra.reshape(self.nwalkers, self.nlat)
+
     # -- chain synchronisation (mc_check_chain_synchronisation, mc_moves.F90:2217-2416) -------------------------
     def set_reference(self):
         """Remember the reference configuration (ref_hmatrix / ref_ljr of init.f90:90,106) from the host's current
