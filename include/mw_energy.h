@@ -215,7 +215,16 @@ int mw_local_energy(int ils, int imol, double *e);
 /* The drop-in form: first mirror up to two host positions (the molecule being
  * queried and the one queried just before it, whose host position may have
  * been silently reverted), then evaluate -- one launch.  imol_prev <= 0 or
- * r_prev == NULL skips the second patch. */
+ * r_prev == NULL skips the second patch.
+ * The contract: every position a call carries (r_imol; r_prev when imol_prev >= 1
+ * and imol_prev != imol) is COMMITTED to the mirrored positions, r_prev first, and
+ * the energy is that of imol in the mirrored box after both.  `prev` is a
+ * convenience for the caller's silent reverts, not a duty: a call may omit it, or
+ * name a molecule other than the one asked about last, and every later call still
+ * sees every committed position (the resident server then brings its per-molecule
+ * moments up to date from the mirrored box before it answers, which costs that one
+ * call a load level; the caller that always passes the molecule it asked about last
+ * never pays it). */
 int mw_local_energy_patched(int ils, int imol, const double r_imol[3],
                             int imol_prev, const double r_prev[3], double *e);
 /* The same call split in two, for a host that knows its NEXT question while it still waits for the answer to this
@@ -223,9 +232,17 @@ int mw_local_energy_patched(int ils, int imol, const double r_imol[3],
  * that lattice's mail slot and returns, `collect` waits for its reply.  One posted request per lattice at a time; any
  * other single call on that lattice waits for it first.  Both return 2 -- not an error, no message -- when there is
  * nothing to gain or to collect: the resident server is off (MW_LOCAL_SERVER=0), nothing was posted, or an entry
- * point that changes device state ran in between (the reply may predate it: ask again with mw_local_energy_patched). */
+ * point that changes device state ran in between (the reply may predate it: ask again with mw_local_energy_patched).
+ * Lattices ils and ils + 8 share a mail slot: a single call or a post on one of them waits for the other's posted
+ * request and drops its reply, and the other's collect then returns 2 as well -- never another lattice's energy.  A
+ * request that was posted is carried out either way: its positions are committed whether or not its reply is collected. */
 int mw_local_energy_post(int ils, int imol, const double r_imol[3], int imol_prev, const double r_prev[3]);
 int mw_local_energy_collect(int ils, double *e);
+/* Diagnostics for tests and tools: which routine of the resident server answered the single calls of box ils since
+ * mw_init.  out = {moment path, scanning routine, plain routine, moment updates (of a prev that had moved, or of a
+ * molecule no request covered), launches of the server (whole context)}.  An exclusive entry point: it stops the
+ * server first.  With MW_LOCAL_SERVER=0 nothing is served and all five stay 0. */
+int mw_server_counts(int ils, long long out[5]);
 
 /* Batched single-move path: request m is (ils[m], imol[m]) and, if trial_xyz
  * is not NULL, molecule imol[m] is evaluated AT trial_xyz[3m..3m+2] without

@@ -156,8 +156,12 @@ struct Ctx {
     unsigned long long sseq[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long spend[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // per slot: sequence number of a posted, not yet collected request (0: none)
     unsigned long long spend_epoch[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int spend_box[8] = {0, 0, 0, 0, 0, 0, 0, 0};                // ... and the lattice it belongs to (a slot serves every nslots-th lattice)
     hipEvent_t ev_srv = nullptr;                     // the server's stream waits on it for the moments made on the main stream
     double* d_pm = nullptr; int* d_srvmomok = nullptr;   // the resident server's moment path: the positions its moments were made from [nbox][N][3]; per box, still in step
+    int* d_srvunc = nullptr;                         // ... per box, the molecule whose committed position d_pm does not hold yet (-1: none)
+    unsigned long long* d_srvcounts = nullptr;       // [nbox][4] since mw_init: requests by routine, moment updates (mw_server_counts)
+    long long srv_starts = 0;                        // launches of the server since mw_init
     // staged moves (mw_host_moves.hip.h)
     int mcap = 0, mn = 0;
     int* d_mimol = nullptr;

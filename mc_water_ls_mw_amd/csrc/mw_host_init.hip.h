@@ -130,6 +130,7 @@ static int init_impl(int device, int nwater, int nboxes, int maxneigh)
     HIPCHK(hipHostGetDevicePointer((void**)&g.d_stage, g.h_stage, 0));
     {   // mail slots of the resident local-energy server: one per lattice, at most 8
         g.nslots = std::min(nboxes, 8);
+        if (dev_alloc_zeroed(g.d_srvcounts, nb * 4)) return 1;
         HIPCHK(hipStreamCreateWithFlags(&g.sstream, hipStreamNonBlocking));
         HIPCHK(hipHostMalloc((void**)&g.h_head, sizeof(mw::MailHead), hipHostMallocMapped));
         HIPCHK(hipHostMalloc((void**)&g.h_slots, sizeof(mw::MailSlot) * 8, hipHostMallocMapped));

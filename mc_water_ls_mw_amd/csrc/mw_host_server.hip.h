@@ -26,12 +26,14 @@ static int server_start_locked()
         bool okm = launch_model_energy(1, g.nbox, true, false) == 0 && g.d_mom != nullptr;
         if (okm && !g.d_pm) okm = dev_alloc(g.d_pm, (size_t)g.nbox * g.N * 3) == 0;
         if (okm && !g.d_srvmomok) okm = dev_alloc(g.d_srvmomok, (size_t)g.nbox) == 0;
+        if (okm && !g.d_srvunc) okm = dev_alloc(g.d_srvunc, (size_t)g.nbox) == 0;
         if (okm) okm = ensure_event(g.ev_srv, hipEventDisableTiming) == 0;
         if (okm) {
             // (no host wait: the server's stream waits for the moments on the device -- 52 -> 20-odd us per server start, which a host
             //  with volume moves pays every few dozen calls; "still in step" = any non-zero word)
             okm = hipMemcpyAsync(g.d_pm, g.d_pos, (size_t)g.nbox * g.N * 3 * sizeof(double), hipMemcpyDeviceToDevice, g.stream) == hipSuccess
                && hipMemsetAsync(g.d_srvmomok, 1, (size_t)g.nbox * sizeof(int), g.stream) == hipSuccess
+               && hipMemsetAsync(g.d_srvunc, 0xff, (size_t)g.nbox * sizeof(int), g.stream) == hipSuccess      // (-1: d_pm is d_pos)
                && hipEventRecord(g.ev_srv, g.stream) == hipSuccess
                && hipStreamWaitEvent(g.sstream, g.ev_srv, 0) == hipSuccess;
         }
@@ -41,7 +43,7 @@ static int server_start_locked()
     }
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(g.nslots), dim3(64), 0, g.sstream, g.d_head, g.d_slots, g.d_req, g.d_pos, g.d_ivect,
-                           g.d_nivect, g.d_listm, g.d_nn, g.N, g.ivcap, 300000LL, stamps ? 1 : 0, mom, g.d_pm, g.d_srvmomok);
+                           g.d_nivect, g.d_listm, g.d_nn, g.N, g.ivcap, 300000LL, stamps ? 1 : 0, mom, g.d_pm, g.d_srvmomok, g.d_srvunc, g.d_srvcounts);
     };
     if (plain) launch(mw::k_local_server<false>);
     else       launch(mw::k_local_server<true>);
@@ -49,6 +51,7 @@ static int server_start_locked()
     if (sw) (void)hipSetDevice(prev);
     if (err != hipSuccess) return fail("mw: launching the local-energy server failed: %s", hipGetErrorString(err));
     g.srv_running = true;
+    ++g.srv_starts;
     return 0;
 }
 
@@ -208,9 +211,10 @@ int mw_local_energy(int ils, int imol, double* e) { return mw_local_energy_patch
 
 // The call split in two, for a host that knows its NEXT question while it still waits for the answer to this one (the two
 // lattices of a move, mc_moves.F90:1006-1018): post does not wait, collect does.  One posted request per lattice at a time;
-// any other single call on that lattice waits for it first.  Both return 2 -- not an error, no message -- when there is
-// nothing to gain or to collect: the resident server is switched off (MW_LOCAL_SERVER=0), nothing was posted, or an entry
-// point that changes device state ran in between (the reply may predate it: ask again).
+// any other single call on that lattice -- or on another lattice of its mail slot (lattices ils and ils + 8 share one) -- waits
+// for it first and drops its reply.  Both return 2 -- not an error, no message -- when there is nothing to gain or to collect:
+// the resident server is switched off (MW_LOCAL_SERVER=0), nothing was posted for THIS lattice (or its reply was dropped), or an
+// entry point that changes device state ran in between (the reply may predate it: ask again).
 int mw_local_energy_post(int ils, int imol, const double r_imol[3], int imol_prev, const double r_prev[3])
 {
     if (!g_srv_enabled.load(std::memory_order_acquire)) return 2;
@@ -231,6 +235,7 @@ int mw_local_energy_post(int ils, int imol, const double r_imol[3], int imol_pre
     unsigned long long seq = 0;
     if (server_post(sl, ils, imol, o1, o2, &seq)) return 1;
     g.spend[sl] = seq;
+    g.spend_box[sl] = ils;
     g.spend_epoch[sl] = g_epoch.load(std::memory_order_relaxed);
     return 0;
 }
@@ -243,10 +248,26 @@ int mw_local_energy_collect(int ils, double* e)
     const int sl = (ils - 1) % g.nslots;
     std::lock_guard<std::mutex> slk(g_slot_mu[sl]);
     const unsigned long long ps = g.spend[sl];
-    if (!ps) return 2;
+    if (!ps || g.spend_box[sl] != ils) return 2;              // (nothing posted -- or what is pending belongs to another lattice of this slot,
+                                                              //  whose post waited for and dropped this lattice's reply: ask again)
     g.spend[sl] = 0;
     if (server_wait(sl, ps, e)) return 1;
     return g.spend_epoch[sl] == g_epoch.load(std::memory_order_relaxed) ? 0 : 2;
+}
+
+// Which routine served the single calls of box ils since mw_init, for tests and tools: out = {moment path, scanning routine, plain
+// routine, moment updates (of a prev, or of a molecule no request covered), server launches of the whole context}.  An exclusive
+// entry point: the server is stopped first, so its counters are complete.  (MW_LOCAL_SERVER=0 serves nothing: zeros.)
+int mw_server_counts(int ils, long long out[5])
+{
+    MW_LOCK;
+    if (check_live() || check_box(ils)) return 1;
+    if (!out) return fail("mw_server_counts: out is NULL");
+    unsigned long long c[4];
+    HIPCHK(hipMemcpy(c, g.d_srvcounts + 4 * (size_t)(ils - 1), sizeof c, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 4; ++k) out[k] = (long long)c[k];
+    out[4] = g.srv_starts;
+    return 0;
 }
 
 }  // extern "C"

@@ -52,7 +52,10 @@ void k_local_server(MailHead* __restrict__ head, MailSlot* __restrict__ slots, c
                     double* __restrict__ pos, const double* __restrict__ ivect, const int* __restrict__ nivect,
                     const uint32_t* __restrict__ listm, const int* __restrict__ nn,
                     int N, int ivcap, long long idle_limit, int stamps,
-                    double* mom, double* pm, int* momok)   // the moment path (below), or nullptr
+                    double* mom, double* pm, int* momok,   // the moment path (below), or nullptr
+                    int* unc,                               // per box: the molecule whose committed position pm does not hold yet, or -1
+                    unsigned long long* __restrict__ counts)   // per box: requests served by the moment path / the scanning routine /
+                                                               // the plain routine, moment updates (mw_server_counts)
 {
     __shared__ WaveScratch ws;
     const int lane = threadIdx.x & 63;
@@ -99,13 +102,19 @@ void k_local_server(MailHead* __restrict__ head, MailSlot* __restrict__ slots, c
             // THE MOMENT PATH (round 4; move_energy_mom_wave<SWEEP>, as in the Monte Carlo driver): `mom` = every molecule's moments of
             // the served boxes, made by the full-box kernel when the server starts, and `pm` = the positions they were made FROM.  The
             // host changes positions only through the requests' own overrides -- the queried molecule and the one queried before it
-            // (anything else is an exclusive entry point, which stops the server) -- so at most `prev` can have moved since: if its
+            // (anything else is an exclusive entry point, which stops the server) -- so for the drop-in's caller at most `prev` can have moved since: if its
             // committed position is no longer the one in `pm`, its neighbours' moments and its own are brought up to date first
             // (moments_commit: an accepted move of the host's chain, one request in four at most), then the queried molecule is
             // evaluated with pm[i] as the "old" position -- the arm the moments hold -- and the request's as the trial one.
             // Every neighbour is read from `pm`.  A request this does not cover (an uncommitted override of prev, a decline) takes the
             // routines below; one that leaves the moments behind (a declined update) switches the path off for the box.
+            // A caller need not name `prev` (mw_local_energy has none), or may name another molecule than the one it asked about last:
+            // that molecule's override was committed to `pos` after its reply, and `pm` never heard of it.  unc[b] names it -- the one
+            // molecule of the box whose committed position may differ from pm -- and a request whose i and prev do not cover it brings
+            // it up to date first, from `pos`, the same way as prev.
             bool served = false;
+            int path = 2, nupd = 0;                                     // (for the counters: 0 moment path, 1 scanning routine, 2 plain routine)
+            int un = -1;
             if (mom != nullptr) {
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // (this wavefront's own earlier writes to mom / pm: past the L1)
                 double* MOMb = mom + (size_t)b * N * kMomStride;
@@ -114,6 +123,7 @@ void k_local_server(MailHead* __restrict__ head, MailSlot* __restrict__ slots, c
                 // ONE round trip for everything the path needs to get going (a lone wavefront pays ~0.5 us per dependent load level)
                 const int pv = o2.idx >= 0 ? prev : i;
                 const int mk = momok[b];
+                un = __hip_atomic_load(unc + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (written after the previous reply: past the L1)
                 double px, py, pz, qx, qy, qz;
                 getpm(pv, px, py, pz);
                 getpm(i, qx, qy, qz);
@@ -122,29 +132,42 @@ void k_local_server(MailHead* __restrict__ head, MailSlot* __restrict__ slots, c
                 unsigned int nocounts[4];
                 int cnt = 0;
                 bool ok = true;
-                if (o2.idx >= 0 && o2.idx != i && (px != o2.x || py != o2.y || pz != o2.z)) {       // prev has moved since its moments were made
-                    if (!(flags & 1) || mk == 0) ok = false;       // (an override that is not committed: the moments must not follow it)
-                    else {
-                        MoveRes r2;
-                        if (move_energy_mom_wave<true, 0, 2>(getpm, getiv, nnof, MOMb, &ws, nullptr, prev, nnof(prev), row(prev, lane & 31),
-                                                                 px, py, pz, o2.x, o2.y, o2.z, lane, r2, nocounts, &cnt)) {
-                            moments_commit(MOMb, &ws, prev, cnt, px, py, pz, o2.x, o2.y, o2.z, lane);
-                            if (lane == 0) { PMb[3 * prev] = o2.x; PMb[3 * prev + 1] = o2.y; PMb[3 * prev + 2] = o2.z; }
-                            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                        } else {
-                            ok = false;
-                            if (lane == 0) momok[b] = 0;           // (the moments no longer follow the positions: off for this box until the server restarts)
-                            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                        }
+                const bool late = un >= 0 && un != i && un != o2.idx && mk != 0;    // (the protocol's own caller never is: one more load level)
+                // prev has moved since its moments were made (not: a silent revert, nothing to follow) -- decided HERE, on the loads of the
+                // round trip above: left to the loop below, the compiler sinks pm[prev]'s load into it, a load level of its own
+                const bool moved = (o2.idx >= 0) & (o2.idx != i) & ((px != o2.x) | (py != o2.y) | (pz != o2.z));
+#pragma unroll 1
+                for (int pass = late ? 0 : 1; pass < (moved ? 2 : 1) && ok; ++pass) {   // the molecules whose moments are behind: unc[b], then prev
+                    const int u = pass == 0 ? un : prev;
+                    double ox = px, oy = py, oz = pz, nx = o2.x, ny = o2.y, nz = o2.z;
+                    if (pass == 0) {
+                        const Override none = {-1, 0.0, 0.0, 0.0};
+                        getpm(u, ox, oy, oz);
+                        load_pos<COHERENT>(P, u, none, none, nx, ny, nz);
+                        if (ox == nx && oy == ny && oz == nz) continue;             // (it was asked about where it already was)
+                    } else if (!(flags & 1) || mk == 0) { ok = false; break; }      // (prev's override is not committed: the moments must not
+                                                                                    //  follow it; the uncovered molecule's position already is)
+                    MoveRes r2;
+                    if (move_energy_mom_wave<true, 0, 2>(getpm, getiv, nnof, MOMb, &ws, nullptr, u, nnof(u), row(u, lane & 31),
+                                                             ox, oy, oz, nx, ny, nz, lane, r2, nocounts, &cnt)) {
+                        moments_commit(MOMb, &ws, u, cnt, ox, oy, oz, nx, ny, nz, lane);
+                        if (lane == 0) { PMb[3 * u] = nx; PMb[3 * u + 1] = ny; PMb[3 * u + 2] = nz; }
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                        ++nupd;
+                    } else {
+                        ok = false;
+                        if (lane == 0) momok[b] = 0;               // (the moments no longer follow the positions: off for this box until the server restarts)
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
                     }
                 }
                 if (ok && move_energy_mom_wave<true, 0, 2>(getpm, getiv, nnof, MOMb, &ws, nullptr, i, ni, erow,
-                                                               qx, qy, qz, xi, yi, zi, lane, res, nocounts, &cnt) && mk != 0) { e = res.en; served = true; }
+                                                               qx, qy, qz, xi, yi, zi, lane, res, nocounts, &cnt) && mk != 0) { e = res.en; served = true; path = 0; }
             }
             if (served) {
             } else if (move_energy_wave(getpos, getiv, row, nnof, &ws, nivect[b], i, nnof(i), row(i, lane & 31), xi, yi, zi, xi, yi, zi, lane, res)) {
                 e = res.eo;
+                path = 1;
             } else {
                 unsigned int ni, ns;
                 e = local_energy_wave_batched<COHERENT>(P, IVb, LMb, NNb, i, o1, o2, lane, ni, ns);
@@ -173,6 +196,14 @@ void k_local_server(MailHead* __restrict__ head, MailSlot* __restrict__ slots, c
                         __hip_atomic_store(P + 3 * o2.idx + 2, o2.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     }
                 }
+                // still after the reply, off the caller's chain: who is uncovered now, and the box's counters (fire-and-forget adds: this
+                // wavefront is the only writer of its boxes' counters, the add is atomic only to spare the wait a load would take)
+                if (mom != nullptr) {
+                    const int now = ((flags & 1) && o1.idx >= 0) ? i : (un == i ? i : -1);
+                    if (now != un) __hip_atomic_store(unc + b, now, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                (void)__hip_atomic_fetch_add(counts + 4 * (size_t)b + path, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (nupd) (void)__hip_atomic_fetch_add(counts + 4 * (size_t)b + 3, (unsigned long long)nupd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             last = seq;
             idle = 0;

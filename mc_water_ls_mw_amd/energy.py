@@ -45,7 +45,7 @@ ABI_SYMBOLS = (
     "mw_ice_clusters", "mw_ice_clusters_batch", "mw_ice_clusters_launch", "mw_ice_clusters_plan", "mw_ice_clusters_last",
     "mw_rdf", "mw_rdf_batch", "mw_rdf_launch",
     "mw_local_energy", "mw_local_energy_patched", "mw_local_energy_post", "mw_local_energy_collect",
-    "mw_local_energy_batch", "mw_delta_energy_batch",
+    "mw_server_counts", "mw_local_energy_batch", "mw_delta_energy_batch",
     "mw_moves_upload", "mw_moves_launch", "mw_moves_fetch", "mw_moves_counts",
     "mw_model_energy_launch", "mw_step_launch", "mw_model_energy_fetch", "mw_build_neighbours_launch", "mw_sync",
     "mw_timer_start", "mw_timer_stop", "mw_timer_elapsed_ms", "mw_device_info",
@@ -573,6 +573,14 @@ class EnergyModule:
                 self._chk(self._local(ils, imol, _d(r), 0, None, eref))
         self._last_imol[b] = imol
         return e.value
+
+    def server_counts(self, ils):
+        """Which routine of the resident server answered the single calls of lattice ils since ``energy_init``:
+        {"moments", "scan", "plain", "updates", "starts"} (mw_server_counts; it stops the server, like every exclusive entry)."""
+        self._ils(ils)
+        out = (ctypes.c_longlong * 5)()
+        self._chk(self.L.mw_server_counts(ils, out))
+        return dict(zip(("moments", "scan", "plain", "updates", "starts"), (int(v) for v in out)))
 
     # -- batched single-move path -----------------------------------------------------
     def local_energy_batch(self, ils, imol, trial_xyz=None):
