@@ -25,7 +25,9 @@ namespace mw {
 //   MOMPATH only -- bit 3: count (the interactions and slots of the served requests, summed per item into `mtot`, and the zero words
 //   of `counts`: without it the launch computes and writes nothing of them), bit 4: no energy output (nothing written to e_old or
 //   e_new, nothing appended to `declined`: the pass that counts on demand, mw_moves_counts), bit 5: sort the item's requests by
-//   their number of in-range neighbours before evaluating them (below; MW_MOVE_SORT=0 clears it)
+//   their number of in-range neighbours before evaluating them (below; MW_MOVE_SORT=0 clears it), bit 6: the pass that counts for
+//   the sort keeps every request's row-slot mask, and a group rebuilds its queues from the masks instead of scanning the rows again
+//   (THE MASK WALK, mw_move_lanes.hip.h; only where bit 5 sorts; MW_MOVE_MASKS=0 clears it)
 constexpr int kMoveChunk = 2048;   // requests per work item when the box is staged in LDS
 
 // MOMPATH keeps an item's requests in LDS as 32-bit KEYS: molecule | request index in the item << 13 | nq << 24, nq = the entries
@@ -40,6 +42,13 @@ constexpr int kSortChunks = kMoveChunk / 64;                               // a 
 static_assert(kMoveChunk <= (1 << kKeyReqBits) && kKeyNqOver < (1 << kKeyNqBits) && kKeyNqShift + kKeyNqBits <= 32, "the key's fields");
 static_assert(kSortChunks == 2 * 16, "two rounds of the sixteen wavefronts rank an item's keys: chunks v and v + 16 in wavefront v");
 static_assert((kSortChunks + 1) * kSortBins * sizeof(uint32_t) <= 16 * sizeof(WaveScratch), "the sort's tables are overlaid on the idle queues");
+// MOMPATH's use of the sixteen WaveScratch blocks: the queues of wavefront v at byte v * kQueueBytes, and behind the sixteen queues
+// the item's row-slot masks (mode bit 6), one word per request, indexed by the request's index in the item as uploaded.
+constexpr size_t kQueueBytes = kLaneQueueWords * sizeof(uint32_t);
+constexpr size_t kMaskTableAt = 16 * kQueueBytes;
+static_assert(kMaskTableAt + kMoveChunk * sizeof(uint32_t) <= 16 * sizeof(WaveScratch), "the queues and the mask table fit the scratch blocks: no new LDS");
+static_assert((kSortChunks + 1) * kSortBins * sizeof(uint32_t) <= kMaskTableAt, "the sort's tables lie on the queues and end before the masks");
+static_assert(kMaskTableAt % 16 == 0 && kQueueBytes % 16 == 0, "alignment of the queues and of the mask table");
 
 // (LAYOUT: SoA measures 1.4 % faster than the paired layout here -- 1288 vs 1306 us, tools/kbench -- now that the scan
 // reads one vector less per slot; the full-box kernel keeps the paired layout, where it is the faster one)
@@ -163,10 +172,12 @@ void k_move_energy(const double* __restrict__ pos, const double* __restrict__ iv
         //  uploaded, 594 / 1424 by nq; 782 / 2400 by the old position's in-range count, 809 / 2558 by row length, 751 / 2248 by a
         //  bound from the displacement.)
         //
-        // What a request brings from global memory -- its slot in the caller's order, its trial position, the first four entries of its
-        // molecule's row -- each lane asks for itself with vector loads, for the NEXT group, before the current group's result stores:
-        // the stores wait for nothing, and the loads are in flight across them and the ticket.  The count pass asks one group ahead too.
-        uint32_t* wq = reinterpret_cast<uint32_t*>(ws);
+        // What a request brings from global memory -- its slot in the caller's order, its trial position, and of its molecule's row the
+        // entries its mask names (a group that walks the masks, below) or the first four (a group that scans) -- each lane asks for
+        // itself with vector loads, for the NEXT group, before the current group's result stores: the stores wait for nothing, and the
+        // loads are in flight across them and the ticket.  The count pass asks one group ahead too.
+        uint32_t* wq = reinterpret_cast<uint32_t*>(ws - wave) + wave * kLaneQueueWords;
+        uint32_t* smask = reinterpret_cast<uint32_t*>(ws - wave) + kMaskTableAt / sizeof(uint32_t);
         unsigned char* qn = s_qn + wave * 32;
         const double* MOM = mom + (size_t)b * N * kMomStride;
         const int rq = lane >> 1, side = lane & 1;
@@ -199,8 +210,12 @@ void k_move_energy(const double* __restrict__ pos, const double* __restrict__ iv
                 const int n_i = q < nreq ? min(nnof(i), kRow) : 0;
                 int cnt = 0;
                 bool self = false;
-                lanes_scan<false>(image, LM + (size_t)i * kRow, wq, rq, i, n_i, c4, px, py, pz, cnt, self);
-                if (q < nreq && side == 0) skey[q] = k | (uint32_t)(self || cnt > kLaneQueue ? kKeyNqOver : cnt) << kKeyNqShift;
+                uint32_t msk = 0u;
+                lanes_scan<false>(image, LM + (size_t)i * kRow, wq, rq, i, n_i, c4, px, py, pz, cnt, self, msk);
+                if (q < nreq && side == 0) {
+                    skey[q] = k | (uint32_t)(self || cnt > kLaneQueue ? kKeyNqOver : cnt) << kKeyNqShift;
+                    if (mode & 64) smask[q] = n_i > 32 ? kMaskScan : msk;   // (q = the request's index in the item as uploaded)
+                }
                 k = k_nx; t[0] = t_nx[0]; t[1] = t_nx[1]; t[2] = t_nx[2]; c4 = c_nx;
             }
             __syncthreads();
@@ -258,38 +273,55 @@ void k_move_energy(const double* __restrict__ pos, const double* __restrict__ iv
                 }
         }
         const int ngrp = (nserve + 31) >> 5;
-        auto fetch = [&](int grp, int& i_, int& o_, double (&t_)[3], uint4& c_) {
-            i_ = 0; o_ = 0; t_[0] = t_[1] = t_[2] = 0.0; c_ = make_uint4(0u, 0u, 0u, 0u);
+        // A group WALKS THE MASKS (mw_move_lanes.hip.h) when the item was counted and sorted above with mode bit 6 and none of its
+        // requests holds kMaskScan; else it scans its rows as the count pass did.  The decision is the wavefront's, made where the
+        // group is fetched: a walking group's lanes bring the row entries at their set bits, up to kLaneWalk each, a scanning group's
+        // the first four entries of their rows -- in the same registers.  (A lane past the end has an empty mask and loads nothing.)
+        const bool masks = (mode & 64) && (mode & 32) && nreq > 32;
+        auto fetch = [&](int grp, uint32_t& k_, int& o_, double (&t_)[3], uint32_t (&e_)[kLaneWalk], bool& walk_) {
+            k_ = 0u; o_ = 0; t_[0] = t_[1] = t_[2] = 0.0; walk_ = false;
+#pragma unroll
+            for (int c = 0; c < kLaneWalk; ++c) e_[c] = 0u;
             if (grp < ngrp) {
-                const uint32_t k_ = skey[min(grp * 32 + rq, nserve - 1)];   // (a lane past the end repeats the last request and serves nothing)
+                k_ = skey[min(grp * 32 + rq, nserve - 1)];        // (a lane past the end repeats the last request and serves nothing)
                 const unsigned m_ = (unsigned)w.y + ((k_ >> kKeyReqShift) & kKeyReqMask);
-                i_ = (int)(k_ & kKeyMolMask);
-                c_ = *reinterpret_cast<const uint4*>(LM + (size_t)i_ * kRow);
+                const unsigned at = (k_ & kKeyMolMask) * (unsigned)kRow;
+                if (masks) {
+                    const uint32_t msk = grp * 32 + rq < nserve ? smask[(k_ >> kKeyReqShift) & kKeyReqMask] : 0u;
+                    walk_ = __ballot(msk == kMaskScan) == 0ull;
+                    if (walk_) lanes_entries(LM, at, msk, side, e_);
+                }
+                if (!walk_) {
+                    const uint4 c_ = *reinterpret_cast<const uint4*>(LM + at);
+                    e_[0] = c_.x; e_[1] = c_.y; e_[2] = c_.z; e_[3] = c_.w;
+                }
                 if (mode & 2) { t_[0] = req_trial[3u * m_]; t_[1] = req_trial[3u * m_ + 1u]; t_[2] = req_trial[3u * m_ + 2u]; }
                 o_ = perm[m_];
             }
         };
         int cur = wave;
-        int i, o; double t[3]; uint4 c4;
-        fetch(cur, i, o, t, c4);
+        uint32_t k; int o; double t[3]; uint32_t e8[kLaneWalk]; bool walk;
+        fetch(cur, k, o, t, e8, walk);
         while (cur < ngrp) {
             int nxt = 0;
             if (lane == 0) nxt = __hip_atomic_fetch_add(&s_next, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             nxt = __builtin_amdgcn_readfirstlane(nxt);
-            int i_nx, o_nx; double t_nx[3]; uint4 c_nx;
+            uint32_t k_nx; int o_nx; double t_nx[3]; uint32_t e_nx[kLaneWalk]; bool walk_nx;
             const bool valid = cur * 32 + rq < nserve;
+            const int i = (int)(k & kKeyMolMask);
             double px, py, pz;                                    // this lane's position: the old one, in the odd lane the trial one
             getpos(i, px, py, pz);
             if ((mode & 2) && side) { px = t[0]; py = t[1]; pz = t[2]; }
             const int n_i = valid ? min(nnof(i), kRow) : 0;
             double en = 0.0;
             unsigned int ci = 0u, cs = 0u;
-            const bool served = move_energy_mom_lanes(getpos, getiv, nnof, LM + (size_t)i * kRow, MOM, wq, qn, i, n_i, c4,
+            const bool served = move_energy_mom_lanes(getpos, getiv, nnof, LM + (size_t)i * kRow, MOM, wq, qn, i, n_i,
+                                                      walk, valid ? (int)(k >> kKeyNqShift) : 0, e8,
                                                       px, py, pz, lane, count, en, ci, cs);
             // (the next group's loads leave HERE, behind the evaluation and ahead of the result stores: issued at the loop's top they
-            //  are thirteen registers held across the evaluation, which has none to spare -- and a group starts on memory once per
-            //  32 requests, with three other wavefronts of the SIMD to fill the wait)
-            fetch(nxt, i_nx, o_nx, t_nx, c_nx);
+            //  are up to seventeen registers held across the evaluation, which has none to spare -- and a group starts on memory once
+            //  per 32 requests, with three other wavefronts of the SIMD to fill the wait)
+            fetch(nxt, k_nx, o_nx, t_nx, e_nx, walk_nx);
             if (valid && !served) {
                 // (declined: more than kLaneQueue in-range neighbours, a triplet the 0.99 rule drops, a molecule that lists itself --
                 //  left to k_move_fallback like the requests the scan builds decline)
@@ -306,7 +338,9 @@ void k_move_energy(const double* __restrict__ pos, const double* __restrict__ iv
                 if (count) { acc[0] += ci; acc[1] += cs; }        // (this lane's side: sorted out below)
             }
             wave_fence();                                         // (the queues are the next group's)
-            cur = nxt; i = i_nx; o = o_nx; t[0] = t_nx[0]; t[1] = t_nx[1]; t[2] = t_nx[2]; c4 = c_nx;
+            cur = nxt; k = k_nx; o = o_nx; t[0] = t_nx[0]; t[1] = t_nx[1]; t[2] = t_nx[2]; walk = walk_nx;
+#pragma unroll
+            for (int c = 0; c < kLaneWalk; ++c) e8[c] = e_nx[c];
         }
     } else {
         int cur = wave;

@@ -14,7 +14,8 @@ namespace mw {
 // requests: lanes 2r and 2r + 1 serve request r of the group at the old and at the trial position, in lockstep over the same entries,
 // the way the full-box kernel serves a molecule per lane (mw_full_energy.hip.h: atom_energy).
 //   phase 1  both lanes walk the n_i slots of i's row (up to kRow: no 32-slot limit), each against its own position, and park the
-//            entries in range of EITHER position, in row order, in the request's queue in LDS;
+//            entries in range of EITHER position, in row order, in the request's queue in LDS (or rebuild that queue from the mask
+//            an earlier scan of the same row left: THE MASK WALK below);
 //   phase 2  over the queue: the pair term and i's arm into the lane's own running sums (MomentSums: the j--i--k sum is
 //            1/2 [(|S2|^2 - Q) - 2 c0 (|S1|^2 - Q) + c0^2 (S0^2 - Q)] of them, no pair loop), and the i--j--k sum from j's moments less
 //            i's OLD arm, as in move_energy_mom_wave.
@@ -55,10 +56,12 @@ __device__ __forceinline__ void lanes_image(PosFn getpos, IvFn getiv, uint32_t e
 // against its own position (px, py, pz): four slots per load, one load ahead (the last one wraps to the row's start: never used).
 // `cnt` = the entries in range of EITHER position, `self` = the row names i itself.  STORE: the first kLaneQueue of them are parked
 // in the request's queue, in row order (phase 1 of move_energy_mom_lanes); without it nothing is written (the count pass of
-// k_move_energy, which sorts an item's requests by `cnt` before any of them is evaluated).  The loop is wave-uniform.
+// k_move_energy, which sorts an item's requests by `cnt` before any of them is evaluated) and `msk` gets bit s set for every
+// counted slot s < 32: the request's ROW-SLOT MASK, which lanes_entries below turns back into the queue.  The loop is wave-uniform.
 template <bool STORE, typename ImageFn>
 __device__ __forceinline__ void lanes_scan(ImageFn image, const uint32_t* __restrict__ rowp, uint32_t* __restrict__ wq, int r,
-                                           int i, int n_i, uint4 first, double px, double py, double pz, int& cnt, bool& self)
+                                           int i, int n_i, uint4 first, double px, double py, double pz, int& cnt, bool& self,
+                                           uint32_t& msk)
 {
     uint4 c4 = first;
     for (int s0 = 0; __ballot(s0 < n_i) != 0ull; s0 += 4) {
@@ -78,6 +81,7 @@ __device__ __forceinline__ void lanes_scan(ImageFn image, const uint32_t* __rest
                 self = self || (has && (int)(ent[h + u] & kJMask) == i);
                 if (inu) {                                       // (both lanes of the pair write the same word)
                     if constexpr (STORE) { if (cnt < kLaneQueue) wq[cnt * 32 + r] = ent[h + u]; }
+                    else msk |= 1u << ((s0 + h + u) & 31);       // (a row longer than 32 slots: its mask is not used)
                     ++cnt;                                       // past the cap: counted, never stored
                 }
             }
@@ -86,28 +90,79 @@ __device__ __forceinline__ void lanes_scan(ImageFn image, const uint32_t* __rest
     }
 }
 
-// One group: this lane's request is molecule `i` (row length n_i; 0 = no request in this lane), its row `rowp` = LM + i * kRow with
-// the first four entries already in `first`, and (px, py, pz) the position this lane evaluates: the old one in the even lane, the
-// trial one in the odd lane.  `wq` = the wavefront's queue words, `qn` = its 32 queue lengths (bytes).  Returns false when the
-// request is declined (the same answer in both lanes of a pair); else `E` = the local energy at this lane's position and, when
-// `count` (wave-uniform), `ci` / `cs` = its interactions and list slots.
+// THE MASK WALK.  The count pass has scanned a sorted item's rows once and kept, per request, the mask lanes_scan<false> makes; a
+// request whose row has more than 32 slots keeps kMaskScan, "scan me" (no served request's mask: that has at most kLaneQueue bits).
+// The main pass rebuilds a queue from its mask instead of scanning again: the set bits in ascending order are the in-range slots in
+// row order, so entry c of the queue is the row's entry at the c-th set bit -- word for word what lanes_scan<true> parks.  The two
+// lanes of a pair share the work: lane `side` LOADS the entries of rank side, side + 2, ... (lanes_entries: kLaneWalk loads at most,
+// the trips wave-uniform) and later PARKS them (lanes_park), so that the loads can be in flight one group ahead.
+constexpr int kLaneWalk = kLaneQueue / 2;
+constexpr uint32_t kMaskScan = 0xffffffffu;
+static_assert(kLaneQueue < 32, "a served request's mask is never kMaskScan");
+
+// `row` = the list of the box, `at` = the first word of this lane's row in it (32 bits: the loads take a scalar base)
+__device__ __forceinline__ void lanes_entries(const uint32_t* __restrict__ row, unsigned at, uint32_t msk, int side, uint32_t (&ent)[kLaneWalk])
+{
+    uint32_t m = side ? msk & (msk - 1u) : msk;                  // (the odd lane starts at the second set bit)
+    bool more = true;                                            // (wave-uniform; no `break`: the loop unrolls, and `ent` stays in registers)
+#pragma unroll
+    for (int c = 0; c < kLaneWalk; ++c) {
+        ent[c] = 0u;
+        more = more && __ballot(m != 0u) != 0ull;
+        if (more) {
+            if (m != 0u) ent[c] = row[at + (unsigned)__builtin_ctz(m)];
+            m &= m - 1u; m &= m - 1u;                            // the lowest two set bits: this lane's and its partner's
+        }
+    }
+}
+
+// entry c of lane `side` is entry 2c + side of the queue of request r; nq = the queue's length (0: no request in this lane)
+__device__ __forceinline__ void lanes_park(uint32_t* __restrict__ wq, int r, int side, int nq, const uint32_t (&ent)[kLaneWalk])
+{
+    uint32_t* __restrict__ mine = wq + side * 32 + r;            // (one address: the eight stores differ by constant offsets)
+    const int left = nq - side;
+    bool more = true;
+#pragma unroll
+    for (int c = 0; c < kLaneWalk; ++c) {
+        more = more && __ballot(2 * c < left) != 0ull;
+        if (more && 2 * c < left) mine[c * 64] = ent[c];
+    }
+}
+
+// One group: this lane's request is molecule `i` (row length n_i; 0 = no request in this lane), its row `rowp` = LM + i * kRow, and
+// (px, py, pz) the position this lane evaluates: the old one in the even lane, the trial one in the odd lane.  `wq` = the
+// wavefront's queue words, `qn` = its 32 queue lengths (bytes).  `walk` (wave-uniform): every request of the group comes with the
+// length of its queue, `nq_key` -- at most kLaneQueue, and no molecule lists itself: the count pass has taken those requests out --
+// and `ent` = what lanes_entries loaded for this lane; else `ent[0..3]` = the first four entries of the row, and phase 1 scans it.
+// Returns false when the request is declined (the same answer in both lanes of a pair); else `E` = the local energy at this lane's
+// position and, when `count` (wave-uniform), `ci` / `cs` = its interactions and list slots.
 template <typename PosFn, typename IvFn, typename NnFn>
 __device__ __forceinline__ bool move_energy_mom_lanes(PosFn getpos, IvFn getiv, NnFn nnof, const uint32_t* __restrict__ rowp,
                                                       const double* __restrict__ MOM, uint32_t* __restrict__ wq, unsigned char* __restrict__ qn,
-                                                      int i, int n_i, uint4 first, double px, double py, double pz,
+                                                      int i, int n_i, bool walk, int nq_key, const uint32_t (&ent)[kLaneWalk],
+                                                      double px, double py, double pz,
                                                       int lane, bool count, double& E, unsigned int& ci, unsigned int& cs)
 {
     const int r = lane >> 1, side = lane & 1;
     auto image = [&](uint32_t e, double& qx, double& qy, double& qz) { lanes_image(getpos, getiv, e, qx, qy, qz); };
 
-    // ---- phase 1: the scan, parking the entries in range of either position in the queue -----------------------------------------
-    int cnt = 0;
-    bool self = false;
-    lanes_scan<true>(image, rowp, wq, r, i, n_i, first, px, py, pz, cnt, self);
-    bool decl = self || cnt > kLaneQueue;
-    if (side == 0) qn[r] = (unsigned char)(cnt < kLaneQueue ? cnt : kLaneQueue);
-    wave_fence();
-    const int nq = (int)qn[r];
+    // ---- phase 1: the entries in range of either position into the queue, from the mask's loads or by the scan --------------------
+    int nq;
+    bool decl = false;
+    if (walk) {
+        lanes_park(wq, r, side, nq_key, ent);
+        wave_fence();
+        nq = nq_key;
+    } else {
+        int cnt = 0;
+        bool self = false;
+        uint32_t none = 0u;
+        lanes_scan<true>(image, rowp, wq, r, i, n_i, make_uint4(ent[0], ent[1], ent[2], ent[3]), px, py, pz, cnt, self, none);
+        decl = self || cnt > kLaneQueue;
+        if (side == 0) qn[r] = (unsigned char)(cnt < kLaneQueue ? cnt : kLaneQueue);
+        wave_fence();
+        nq = (int)qn[r];
+    }
 
     // ---- the 0.99 rule: the queue's pairs, shared between the two lanes --------------------------------------------------------
     bool hard = false;
