@@ -1,7 +1,7 @@
 """Build libmw_hip.so (the C-ABI engine), libmw_comms.so (the RCCL exchange layer for a Fortran host, include/mw_comms.h),
 libmw_sk.so (the structure factor S(k), include/mw_sk.h), libmw_boo.so (the Steinhardt bond-order parameters,
-include/mw_boo.h) and libmw_tet.so (tetrahedral order, d5 and LSI from the sorted nearest neighbours, include/mw_tet.h)
-in-tree with hipcc for gfx950.
+include/mw_boo.h), libmw_tet.so (tetrahedral order, d5 and LSI from the sorted nearest neighbours, include/mw_tet.h) and
+libmw_adf.so (the O-O-O angle distribution, include/mw_adf.h) in-tree with hipcc for gfx950.
 
     python -m mc_water_ls_mw_amd.build [--force]
 
@@ -28,7 +28,7 @@ COMMS_LIB = os.path.join(PKG, "libmw_comms.so")
 COMMS_SRC = os.path.join(CSRC, "mw_comms.hip")
 COMMS_DEPS = [COMMS_SRC, os.path.join(os.path.dirname(PKG), "include", "mw_comms.h")]
 
-LIB_HOST = os.path.join(CSRC, "mw_lib_host.h")       # the host layer libmw_sk.so, libmw_boo.so and libmw_tet.so share; not a dependency of libmw_hip.so
+LIB_HOST = os.path.join(CSRC, "mw_lib_host.h")       # the host layer libmw_sk.so, libmw_boo.so, libmw_tet.so and libmw_adf.so share; not a dependency of libmw_hip.so
 SK_LIB = os.path.join(PKG, "libmw_sk.so")
 SK_SRC = os.path.join(CSRC, "mw_sk.hip")
 SK_DEPS = [SK_SRC, LIB_HOST, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_sk.h")]
@@ -40,6 +40,10 @@ BOO_DEPS = [BOO_SRC, LIB_HOST, os.path.join(CSRC, "mw_common.hip.h"), os.path.jo
 TET_LIB = os.path.join(PKG, "libmw_tet.so")
 TET_SRC = os.path.join(CSRC, "mw_tet.hip")
 TET_DEPS = [TET_SRC, LIB_HOST, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_tet.h")]
+
+ADF_LIB = os.path.join(PKG, "libmw_adf.so")
+ADF_SRC = os.path.join(CSRC, "mw_adf.hip")
+ADF_DEPS = [ADF_SRC, LIB_HOST, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_adf.h")]
 
 
 def hipcc_path():
@@ -95,7 +99,12 @@ def build_tet(force=False, verbose=False):
     return _compile(TET_LIB, [TET_SRC], TET_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
 
 
+def build_adf(force=False, verbose=False):
+    """libmw_adf.so: the O-O-O angle histogram kernels and their C ABI, a translation unit of its own like libmw_tet.so."""
+    return _compile(ADF_LIB, [ADF_SRC], ADF_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
+
+
 if __name__ == "__main__":
     force = "--force" in sys.argv
-    for builder in (build, build_comms, build_sk, build_boo, build_tet):
+    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf):
         print(builder(force=force, verbose=True))

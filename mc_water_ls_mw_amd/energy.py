@@ -520,6 +520,19 @@ class EnergyModule:
         self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
         return tetrahedral.tetrahedral_order(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, r_search_ang, r_lsi_ang)
 
+    # -- O-O-O angle distribution (libmw_adf.so, include/mw_adf.h; no counterpart in the reference) -----------------
+    def angle_counts(self, first_ils=1, count=None, r_cut_ang=3.5, edges=None, group=None, ngroups=1):
+        """(hist [count, ngroups, nbins], counts [count, nwater], summary [count, ngroups, 4]) of ``count`` boxes --
+        angles.angle_counts, ``group`` [count, nwater] or None -- from the positions the DEVICE holds and this module's hmatrix
+        (after device volume moves call ``WalkerFarm.sync_cells`` first).  The positions take one host hop
+        (mw_download_positions_range) on their way to libmw_adf.so, which shares nothing with the engine but the device."""
+        from . import angles
+        count = self.num_lattices - first_ils + 1 if count is None else count
+        self._ils(first_ils), self._ils(first_ils + count - 1)
+        pos = np.zeros((count, self.nwater, 3))
+        self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
+        return angles.angle_counts(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, r_cut_ang, edges, group, ngroups)
+
     def model_energy_counts(self, ils):
         p, t = ctypes.c_longlong(0), ctypes.c_longlong(0)
         self._chk(self.L.mw_model_energy_counts(ils, ctypes.byref(p), ctypes.byref(t)))

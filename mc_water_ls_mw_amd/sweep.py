@@ -366,6 +366,31 @@ class WalkerFarm:
         tetra = (order[:, :, 0] > 0.9).sum(axis=1) / float(self.em.nwater)        # (NaN > 0.9 is False)
         return summary.reshape(self.nwalkers, self.nlat, 8), tetra.reshape(self.nwalkers, self.nlat)
 
+    def angle_distribution(self, r_cut_ang=3.5, nbins=90, by=None):
+        """(theta_deg [nbins], P [nlat, ngroups, nbins], capped [nwalkers, nlat]): the distribution of the O-O-O angle between
+        the neighbours of a molecule within ``r_cut_ang`` (include/mw_adf.h), in ``nbins`` bins uniform in theta over 0..180
+        degrees (theta_deg: their centres, descending), of every lattice: the pair counts summed over the walkers, then each
+        histogram normalised to 1 per degree (zeros where a histogram has no pairs); and the number of centres of every box
+        with more than 32 entries, whose pairs are incomplete.  ``by=None``: one group, every molecule a centre;
+        ``by="ice_class"``: six groups, the CHILL+ class of the centre (energy.ICE_CLASS_NAMES, from ``ice_classes_batch`` at
+        the same radius).  From the positions and cells the device holds (the cells read back through :meth:`sync_cells`
+        first).  P(theta) reads the three-body term of the model directly: its peak sharpens at 109.5 degrees as a lattice
+        freezes."""
+        from . import angles
+        self.sync_cells()
+        if by is None:
+            group, ngroups = None, 1
+        elif by == "ice_class":
+            cls, _ = self.em.ice_classes_batch(1, self.em.num_lattices, r_cut_ang)
+            group, ngroups = cls.astype(np.int32), 6
+        else:
+            raise ValueError(f"angle_distribution: by = {by!r} is neither None nor 'ice_class'")
+        edges = angles.adf_edges(nbins, "theta")
+        hist, _, summary = self.em.angle_counts(1, self.em.num_lattices, r_cut_ang, edges, group, ngroups)
+        total = hist.reshape(self.nwalkers, self.nlat, ngroups, int(nbins)).sum(axis=0)
+        theta_deg, p_theta, _, _ = angles.adf_from_counts(total, edges)
+        return theta_deg, p_theta, summary[:, :, 3].sum(axis=1).reshape(self.nwalkers, self.nlat)
+
     # -- chain synchronisation (mc_check_chain_synchronisation, mc_moves.F90:2217-2416) -------------------------
     def set_reference(self):
         """Remember the reference configuration (ref_hmatrix / ref_ljr of init.f90:90,106) from the host's current
