@@ -27,7 +27,8 @@ namespace mw {
 //   e_new, nothing appended to `declined`: the pass that counts on demand, mw_moves_counts), bit 5: sort the item's requests by
 //   their number of in-range neighbours before evaluating them (below; MW_MOVE_SORT=0 clears it), bit 6: the pass that counts for
 //   the sort keeps every request's row-slot mask, and a group rebuilds its queues from the masks instead of scanning the rows again
-//   (THE MASK WALK, mw_move_lanes.hip.h; only where bit 5 sorts; MW_MOVE_MASKS=0 clears it)
+//   (THE MASK WALK, mw_move_lanes.hip.h; only where bit 5 sorts; MW_MOVE_MASKS=0 clears it), bit 7: the 0.99 rule's pair pass enters
+//   its angle block only for pairs that pass THE GATE (mw_move_lanes.hip.h; MW_MOVE_GATE=0 clears it: every pair with |ab| < cutoff)
 constexpr int kMoveChunk = 2048;   // requests per work item when the box is staged in LDS
 
 // MOMPATH keeps an item's requests in LDS as 32-bit KEYS: molecule | request index in the item << 13 | nq << 24, nq = the entries
@@ -211,7 +212,7 @@ void k_move_energy(const double* __restrict__ pos, const double* __restrict__ iv
                 int cnt = 0;
                 bool self = false;
                 uint32_t msk = 0u;
-                lanes_scan<false>(image, LM + (size_t)i * kRow, wq, rq, i, n_i, c4, px, py, pz, cnt, self, msk);
+                lanes_scan<false>(image, LM + (size_t)i * kRow, wq, rq, side, i, n_i, c4, px, py, pz, cnt, self, msk);
                 if (q < nreq && side == 0) {
                     skey[q] = k | (uint32_t)(self || cnt > kLaneQueue ? kKeyNqOver : cnt) << kKeyNqShift;
                     if (mode & 64) smask[q] = n_i > 32 ? kMaskScan : msk;   // (q = the request's index in the item as uploaded)
@@ -317,7 +318,7 @@ void k_move_energy(const double* __restrict__ pos, const double* __restrict__ iv
             unsigned int ci = 0u, cs = 0u;
             const bool served = move_energy_mom_lanes(getpos, getiv, nnof, LM + (size_t)i * kRow, MOM, wq, qn, i, n_i,
                                                       walk, valid ? (int)(k >> kKeyNqShift) : 0, e8,
-                                                      px, py, pz, lane, count, en, ci, cs);
+                                                      px, py, pz, lane, count, (mode & 128) != 0, en, ci, cs);
             // (the next group's loads leave HERE, behind the evaluation and ahead of the result stores: issued at the loop's top they
             //  are up to seventeen registers held across the evaluation, which has none to spare -- and a group starts on memory once
             //  per 32 requests, with three other wavefronts of the SIMD to fill the wait)

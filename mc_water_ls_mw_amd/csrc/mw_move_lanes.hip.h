@@ -27,9 +27,20 @@ namespace mw {
 // cos(theta_Pab) or cos(theta_Pba) >= 0.99 - 1e-9 (a third body in j's moments; the test of move_energy_mom_wave), and
 // cos(theta_aPb) >= 0.99 - 1e-9 (the j--i--k term the wave routine dropped itself).  All three imply |ab| < cutoff -- an angle
 // below 8.2 degrees between two arms shorter than the cutoff -- and |ab| does not depend on P: the two lanes of a pair SHARE the
-// pairs of the queue between them (lane `side` takes b = a + 1 + side, a + 3 + side, ...) and test |ab|^2 only; on ice it is almost
-// never below the cutoff.  When some lane finds such a pair, every lane takes its partner's b as well (DPP) and tests the angles of
-// its own pair and of its partner's at its OWN position, on squares (no square root).
+// pairs of the queue between them (lane `side` takes b = a + 1 + side, a + 3 + side, ...).  |ab| < cutoff alone is no rare event:
+// a first-shell neighbour is bonded to the second-shell neighbours beside it in the queue (23 % of a queue's pairs on thermal ice),
+// and among a wavefront's 64 pairs one is below the cutoff on 98 % of the trips.  What is rare is THE GATE (mode bit 7 of
+// k_move_energy; MW_MOVE_GATE=0 keeps |ab| < cutoff alone): a lane tests its OWN pair against its own position P and its
+// partner's P' (taken once per group on the DPP network; nothing is exchanged on a trip).  With Q = |Pa|^2, R = |Pb|^2, S = |ab|^2
+// and t = Q + R - S = 2 (a - P).(b - P), the triangle P a b has 4 Area^2 = QR - (t/2)^2, the same number from every vertex, and
+// sin^2 of the angle at a vertex is 4 Area^2 over the product of the two squared sides that meet there.  So
+//      cos^2 >= kappa^2 at SOME vertex   =>   QR - (t/2)^2 <= (1 - kappa^2) max(QR, QS, RS)                    "thin(Q, R, S)"
+// and the gate tests that with kappa = 0.98: the right side is 0.0396 max(..) where a triplet the rule drops has at most 0.0199
+// max(..) on the left -- a factor of two, against a rounding error of a few units in 1e-16 QR.  The sign of the cosine and the
+// in-range conditions are left out, so the pairs the gate passes are a SUPERSET of the pairs the rule drops at either position
+// (tests/test_move_gate_ref.py: no miss among 4e5 constructed triangles), and on thermal ice it passes ~10 pairs per 2048
+// requests.  When some lane's gate fires, every lane takes its partner's b as well (DPP) and tests the angles of its own pair and
+// of its partner's at its OWN position, on squares (no square root): that block, and so `hard`, is what it was without the gate.
 // Also declined: more than kLaneQueue entries in range of either position, and a molecule that lists itself.
 // -------------------------------------------------------------------------------------
 constexpr int kLaneQueue = 16;                                   // queue entries per request (thermal ice: 9.2 on average, never above 16)
@@ -52,41 +63,68 @@ __device__ __forceinline__ void lanes_image(PosFn getpos, IvFn getiv, uint32_t e
     qx = xj + vx; qy = yj + vy; qz = zj + vz;
 }
 
-// THE SCAN of a lane pair over the n_i slots of molecule i's row `rowp` (its first four entries already in `first`), each lane
-// against its own position (px, py, pz): four slots per load, one load ahead (the last one wraps to the row's start: never used).
-// `cnt` = the entries in range of EITHER position, `self` = the row names i itself.  STORE: the first kLaneQueue of them are parked
-// in the request's queue, in row order (phase 1 of move_energy_mom_lanes); without it nothing is written (the count pass of
-// k_move_energy, which sorts an item's requests by `cnt` before any of them is evaluated) and `msk` gets bit s set for every
-// counted slot s < 32: the request's ROW-SLOT MASK, which lanes_entries below turns back into the queue.  The loop is wave-uniform.
+// THE SCAN of a lane pair (lanes 2r and 2r + 1, `side` = 0 and 1) over the n_i slots of molecule i's row `rowp` (its first four
+// entries already in `first`), each lane with its own position (px, py, pz): four slots per load, one load ahead (the last one
+// wraps to the row's start: never used).  `cnt` = the entries in range of EITHER position, `self` = the row names i itself.  The
+// loop is wave-uniform.
+//   STORE   phase 1 of move_energy_mom_lanes: both lanes gather all four slots, each tests them against its own position, and the
+//           first kLaneQueue entries in range of either are parked in the request's queue, in row order.
+//   else    the count pass of k_move_energy, which sorts an item's requests by `cnt` before any of them is evaluated: nothing is
+//           written, and `msk` gets bit s set for every counted slot s < 32 -- the request's ROW-SLOT MASK, which lanes_entries
+//           below turns back into the queue.  Here the pair SPLITS A LOAD'S FOUR SLOTS BY PARITY: lane `side` gathers slots side
+//           and 2 + side only, tests each against its own position and its partner's (the subtraction and the squares its partner
+//           would make, on the same values: the same bits), and the two lanes swap their two "in range of either" bits and the
+//           self bit in ONE exchange per load.  Both assemble the nibble of `msk`, the `cnt` and the `self` that four gathers per
+//           lane and an exchange per slot gave: half the gathers for the same squared distances.
 template <bool STORE, typename ImageFn>
-__device__ __forceinline__ void lanes_scan(ImageFn image, const uint32_t* __restrict__ rowp, uint32_t* __restrict__ wq, int r,
+__device__ __forceinline__ void lanes_scan(ImageFn image, const uint32_t* __restrict__ rowp, uint32_t* __restrict__ wq, int r, int side,
                                            int i, int n_i, uint4 first, double px, double py, double pz, int& cnt, bool& self,
                                            uint32_t& msk)
 {
     uint4 c4 = first;
-    for (int s0 = 0; __ballot(s0 < n_i) != 0ull; s0 += 4) {
-        const uint4 nx = *reinterpret_cast<const uint4*>(rowp + ((s0 + 4) & (kRow - 1)));
-        const uint32_t ent[4] = {c4.x, c4.y, c4.z, c4.w};
+    if constexpr (!STORE) {
+        const double tx = pair_swap_f64(px), ty = pair_swap_f64(py), tz = pair_swap_f64(pz);       // the partner's position
+        for (int s0 = 0; __ballot(s0 < n_i) != 0ull; s0 += 4) {
+            const uint4 nx = *reinterpret_cast<const uint4*>(rowp + ((s0 + 4) & (kRow - 1)));
+            const uint32_t e0 = side ? c4.y : c4.x, e1 = side ? c4.w : c4.z;
+            double q0x, q0y, q0z, q1x, q1y, q1z;
+            image(e0, q0x, q0y, q0z);                            // (two slots' gathers in flight together)
+            image(e1, q1x, q1y, q1z);
+            const bool has0 = s0 + side < n_i, has1 = s0 + 2 + side < n_i;
+            const bool in0 = has0 && (dist2(q0x - px, q0y - py, q0z - pz) < kRcSq || dist2(q0x - tx, q0y - ty, q0z - tz) < kRcSq);   // :272,276
+            const bool in1 = has1 && (dist2(q1x - px, q1y - py, q1z - pz) < kRcSq || dist2(q1x - tx, q1y - ty, q1z - tz) < kRcSq);
+            const bool sf = (has0 && (int)(e0 & kJMask) == i) || (has1 && (int)(e1 & kJMask) == i);
+            const int mine = ((in0 ? 1 : 0) | (in1 ? 4 : 0)) << side | (sf ? 16 : 0);   // bits side and 2 + side: this lane's slots
+            const int both = mine | pair_swap_i32(mine);         // (unconditionally: every lane takes part in the exchange)
+            self = self || (both & 16) != 0;
+            msk |= (uint32_t)(both & 15) << (s0 & 31);           // (a row longer than 32 slots: its mask is not used)
+            cnt += __popc((unsigned)(both & 15));
+            c4 = nx;
+        }
+    } else {
+        for (int s0 = 0; __ballot(s0 < n_i) != 0ull; s0 += 4) {
+            const uint4 nx = *reinterpret_cast<const uint4*>(rowp + ((s0 + 4) & (kRow - 1)));
+            const uint32_t ent[4] = {c4.x, c4.y, c4.z, c4.w};
 #pragma unroll
-        for (int h = 0; h < 4; h += 2) {                         // two slots' gathers in flight together
-            double q[2][3];
+            for (int h = 0; h < 4; h += 2) {                     // two slots' gathers in flight together
+                double q[2][3];
 #pragma unroll
-            for (int u = 0; u < 2; ++u) image(ent[h + u], q[u][0], q[u][1], q[u][2]);
+                for (int u = 0; u < 2; ++u) image(ent[h + u], q[u][0], q[u][1], q[u][2]);
 #pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const bool has = s0 + h + u < n_i;
-                const bool mine = has && dist2(q[u][0] - px, q[u][1] - py, q[u][2] - pz) < kRcSq;   // :272,276
-                const int other = pair_swap_i32(mine ? 1 : 0);   // (unconditionally: every lane takes part in the exchange)
-                const bool inu = mine || other != 0;
-                self = self || (has && (int)(ent[h + u] & kJMask) == i);
-                if (inu) {                                       // (both lanes of the pair write the same word)
-                    if constexpr (STORE) { if (cnt < kLaneQueue) wq[cnt * 32 + r] = ent[h + u]; }
-                    else msk |= 1u << ((s0 + h + u) & 31);       // (a row longer than 32 slots: its mask is not used)
-                    ++cnt;                                       // past the cap: counted, never stored
+                for (int u = 0; u < 2; ++u) {
+                    const bool has = s0 + h + u < n_i;
+                    const bool mine = has && dist2(q[u][0] - px, q[u][1] - py, q[u][2] - pz) < kRcSq;   // :272,276
+                    const int other = pair_swap_i32(mine ? 1 : 0);   // (unconditionally: every lane takes part in the exchange)
+                    const bool inu = mine || other != 0;
+                    self = self || (has && (int)(ent[h + u] & kJMask) == i);
+                    if (inu) {                                   // (both lanes of the pair write the same word)
+                        if (cnt < kLaneQueue) wq[cnt * 32 + r] = ent[h + u];
+                        ++cnt;                                   // past the cap: counted, never stored
+                    }
                 }
             }
+            c4 = nx;
         }
-        c4 = nx;
     }
 }
 
@@ -135,13 +173,13 @@ __device__ __forceinline__ void lanes_park(uint32_t* __restrict__ wq, int r, int
 // length of its queue, `nq_key` -- at most kLaneQueue, and no molecule lists itself: the count pass has taken those requests out --
 // and `ent` = what lanes_entries loaded for this lane; else `ent[0..3]` = the first four entries of the row, and phase 1 scans it.
 // Returns false when the request is declined (the same answer in both lanes of a pair); else `E` = the local energy at this lane's
-// position and, when `count` (wave-uniform), `ci` / `cs` = its interactions and list slots.
+// position and, when `count` (wave-uniform), `ci` / `cs` = its interactions and list slots.  `gate` (wave-uniform): THE GATE above.
 template <typename PosFn, typename IvFn, typename NnFn>
 __device__ __forceinline__ bool move_energy_mom_lanes(PosFn getpos, IvFn getiv, NnFn nnof, const uint32_t* __restrict__ rowp,
                                                       const double* __restrict__ MOM, uint32_t* __restrict__ wq, unsigned char* __restrict__ qn,
                                                       int i, int n_i, bool walk, int nq_key, const uint32_t (&ent)[kLaneWalk],
                                                       double px, double py, double pz,
-                                                      int lane, bool count, double& E, unsigned int& ci, unsigned int& cs)
+                                                      int lane, bool count, bool gate, double& E, unsigned int& ci, unsigned int& cs)
 {
     const int r = lane >> 1, side = lane & 1;
     auto image = [&](uint32_t e, double& qx, double& qy, double& qz) { lanes_image(getpos, getiv, e, qx, qy, qz); };
@@ -157,7 +195,7 @@ __device__ __forceinline__ bool move_energy_mom_lanes(PosFn getpos, IvFn getiv, 
         int cnt = 0;
         bool self = false;
         uint32_t none = 0u;
-        lanes_scan<true>(image, rowp, wq, r, i, n_i, make_uint4(ent[0], ent[1], ent[2], ent[3]), px, py, pz, cnt, self, none);
+        lanes_scan<true>(image, rowp, wq, r, side, i, n_i, make_uint4(ent[0], ent[1], ent[2], ent[3]), px, py, pz, cnt, self, none);
         decl = self || cnt > kLaneQueue;
         if (side == 0) qn[r] = (unsigned char)(cnt < kLaneQueue ? cnt : kLaneQueue);
         wave_fence();
@@ -166,9 +204,17 @@ __device__ __forceinline__ bool move_energy_mom_lanes(PosFn getpos, IvFn getiv, 
 
     // ---- the 0.99 rule: the queue's pairs, shared between the two lanes --------------------------------------------------------
     bool hard = false;
+    const double tx = pair_swap_f64(px), ty = pair_swap_f64(py), tz = pair_swap_f64(pz);           // P': the partner's position
+    constexpr double kThin = 1.0 - 0.98 * 0.98;
+    auto thin = [&](double Q, double R, double S) {              // (the header: QR - (t/2)^2 <= kThin max(QR, QS, RS))
+        const double th = __builtin_fma(0.5, R - S, 0.5 * Q), QR = Q * R;
+        return __builtin_fma(-th, th, QR) <= kThin * fmax(fmax(QR, Q * S), R * S);
+    };
     for (int a = 0; __ballot(a + 1 < nq) != 0ull; ++a) {
         double ax, ay, az;
         image(a + 1 < nq ? wq[a * 32 + r] : 0u, ax, ay, az);
+        double Q = 0.0, Qt = 0.0;
+        if (gate) { Q = dist2(ax - px, ay - py, az - pz); Qt = dist2(ax - tx, ay - ty, az - tz); }
         for (int b0 = a + 1; __ballot(b0 < nq) != 0ull; b0 += 2) {
             const int b = b0 + side;
             const bool live = b < nq;
@@ -177,8 +223,10 @@ __device__ __forceinline__ bool move_energy_mom_lanes(PosFn getpos, IvFn getiv, 
             const double dx = bx - ax, dy = by - ay, dz = bz - az;                                 // a -> b
             const double r2ab = dist2(dx, dy, dz);
             const bool near = live && r2ab < kRcSq;
-            if (__ballot(near) != 0ull) {                        // wave-uniform: every lane is in here, and the exchange below is sound
-                const int near_o = pair_swap_i32(near ? 1 : 0);
+            bool fire = near;
+            if (gate) fire = near && (thin(Q, dist2(bx - px, by - py, bz - pz), r2ab) || thin(Qt, dist2(bx - tx, by - ty, bz - tz), r2ab));
+            if (__ballot(fire) != 0ull) {                        // wave-uniform: every lane is in here, and the exchange below is sound
+                const int fire_o = pair_swap_i32(fire ? 1 : 0);
                 const double ox = pair_swap_f64(bx), oy = pair_swap_f64(by), oz = pair_swap_f64(bz);   // the partner's b
                 constexpr double kC2 = (0.99 - 1e-9) * (0.99 - 1e-9);
                 auto angles = [&](bool on, double cx, double cy, double cz) {
@@ -193,8 +241,8 @@ __device__ __forceinline__ bool move_energy_mom_lanes(PosFn getpos, IvFn getiv, 
                                (dc > 0.0 && dc * dc >= kC2 * (r2a * r2b));
                     }
                 };
-                angles(near, bx, by, bz);
-                angles(near_o != 0, ox, oy, oz);
+                angles(fire, bx, by, bz);
+                angles(fire_o != 0, ox, oy, oz);
             }
         }
     }
