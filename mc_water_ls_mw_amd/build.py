@@ -1,7 +1,8 @@
 """Build libmw_hip.so (the C-ABI engine), libmw_comms.so (the RCCL exchange layer for a Fortran host, include/mw_comms.h),
 libmw_sk.so (the structure factor S(k), include/mw_sk.h), libmw_boo.so (the Steinhardt bond-order parameters,
-include/mw_boo.h), libmw_tet.so (tetrahedral order, d5 and LSI from the sorted nearest neighbours, include/mw_tet.h) and
-libmw_adf.so (the O-O-O angle distribution, include/mw_adf.h) in-tree with hipcc for gfx950.
+include/mw_boo.h), libmw_tet.so (tetrahedral order, d5 and LSI from the sorted nearest neighbours, include/mw_tet.h),
+libmw_adf.so (the O-O-O angle distribution, include/mw_adf.h) and libmw_rings.so (the primitive rings of the bond network,
+include/mw_rings.h) in-tree with hipcc for gfx950.
 
     python -m mc_water_ls_mw_amd.build [--force]
 
@@ -28,7 +29,7 @@ COMMS_LIB = os.path.join(PKG, "libmw_comms.so")
 COMMS_SRC = os.path.join(CSRC, "mw_comms.hip")
 COMMS_DEPS = [COMMS_SRC, os.path.join(os.path.dirname(PKG), "include", "mw_comms.h")]
 
-LIB_HOST = os.path.join(CSRC, "mw_lib_host.h")       # the host layer libmw_sk.so, libmw_boo.so, libmw_tet.so and libmw_adf.so share; not a dependency of libmw_hip.so
+LIB_HOST = os.path.join(CSRC, "mw_lib_host.h")       # the host layer libmw_sk.so, libmw_boo.so, libmw_tet.so, libmw_adf.so and libmw_rings.so share; not a dependency of libmw_hip.so
 SK_LIB = os.path.join(PKG, "libmw_sk.so")
 SK_SRC = os.path.join(CSRC, "mw_sk.hip")
 SK_DEPS = [SK_SRC, LIB_HOST, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_sk.h")]
@@ -44,6 +45,10 @@ TET_DEPS = [TET_SRC, LIB_HOST, os.path.join(CSRC, "mw_common.hip.h"), os.path.jo
 ADF_LIB = os.path.join(PKG, "libmw_adf.so")
 ADF_SRC = os.path.join(CSRC, "mw_adf.hip")
 ADF_DEPS = [ADF_SRC, LIB_HOST, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_adf.h")]
+
+RINGS_LIB = os.path.join(PKG, "libmw_rings.so")
+RINGS_SRC = os.path.join(CSRC, "mw_rings.hip")
+RINGS_DEPS = [RINGS_SRC, LIB_HOST, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_rings.h")]
 
 
 def hipcc_path():
@@ -104,7 +109,12 @@ def build_adf(force=False, verbose=False):
     return _compile(ADF_LIB, [ADF_SRC], ADF_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
 
 
+def build_rings(force=False, verbose=False):
+    """libmw_rings.so: the adjacency and ring-walk kernels and their C ABI, a translation unit of its own like libmw_adf.so."""
+    return _compile(RINGS_LIB, [RINGS_SRC], RINGS_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
+
+
 if __name__ == "__main__":
     force = "--force" in sys.argv
-    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf):
+    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf, build_rings):
         print(builder(force=force, verbose=True))

@@ -533,6 +533,19 @@ class EnergyModule:
         self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
         return angles.angle_counts(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, r_cut_ang, edges, group, ngroups)
 
+    # -- primitive ring statistics (libmw_rings.so, include/mw_rings.h; no counterpart in the reference) ------------
+    def ring_statistics(self, first_ils=1, count=None, r_cut_ang=3.5, list_cap=0):
+        """(hist [count, 5], closed [count, 5], member [count, nwater, 5], counts [count, nwater], summary [count, 4], list
+        [count, list_cap, 8]) of ``count`` boxes -- rings.ring_statistics -- from the positions the DEVICE holds and this
+        module's hmatrix (after device volume moves call ``WalkerFarm.sync_cells`` first).  The positions take one host hop
+        (mw_download_positions_range) on their way to libmw_rings.so, which shares nothing with the engine but the device."""
+        from . import rings
+        count = self.num_lattices - first_ils + 1 if count is None else count
+        self._ils(first_ils), self._ils(first_ils + count - 1)
+        pos = np.zeros((count, self.nwater, 3))
+        self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
+        return rings.ring_statistics(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, r_cut_ang, list_cap)
+
     def model_energy_counts(self, ils):
         p, t = ctypes.c_longlong(0), ctypes.c_longlong(0)
         self._chk(self.L.mw_model_energy_counts(ils, ctypes.byref(p), ctypes.byref(t)))

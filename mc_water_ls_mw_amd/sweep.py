@@ -391,6 +391,17 @@ class WalkerFarm:
         theta_deg, p_theta, _, _ = angles.adf_from_counts(total, edges)
         return theta_deg, p_theta, summary[:, :, 3].sum(axis=1).reshape(self.nwalkers, self.nlat)
 
+    def ring_statistics(self, r_cut_ang=3.5):
+        """(hist [nwalkers, nlat, 5], six [nwalkers, nlat], capped [nwalkers, nlat]): the primitive rings of 3 ... 7 members
+        (include/mw_rings.h) of every lattice of every walker, the mean number of 6-ring nodes a molecule of it is (12 in
+        ice) and the number of its molecules with more than 8 bonds, which have no edges in the ring network.  From the
+        positions and cells the device holds (the cells read back through :meth:`sync_cells` first)."""
+        self.sync_cells()
+        hist, _, member, _, summary, _ = self.em.ring_statistics(1, self.em.num_lattices, r_cut_ang)
+        six = member[:, :, 3].sum(axis=1) / float(self.em.nwater)
+        shape = (self.nwalkers, self.nlat)
+        return hist.reshape(*shape, 5), six.reshape(shape), summary[:, 0].reshape(shape)
+
     # -- chain synchronisation (mc_check_chain_synchronisation, mc_moves.F90:2217-2416) -------------------------
     def set_reference(self):
         """Remember the reference configuration (ref_hmatrix / ref_ljr of init.f90:90,106) from the host's current
