@@ -30,25 +30,27 @@ COMMS_SRC = os.path.join(CSRC, "mw_comms.hip")
 COMMS_DEPS = [COMMS_SRC, os.path.join(os.path.dirname(PKG), "include", "mw_comms.h")]
 
 LIB_HOST = os.path.join(CSRC, "mw_lib_host.h")       # the host layer libmw_sk.so, libmw_boo.so, libmw_tet.so, libmw_adf.so and libmw_rings.so share; not a dependency of libmw_hip.so
+LIB_CELLS = os.path.join(CSRC, "mw_lib_cells.h")     # the cell grid, counting sort and walks of libmw_boo.so, libmw_tet.so, libmw_adf.so and libmw_rings.so; not a
+#                                                     `.hip.h`: DEPS takes every one of those for libmw_hip.so, and libmw_sk.so has no cell grid
 SK_LIB = os.path.join(PKG, "libmw_sk.so")
 SK_SRC = os.path.join(CSRC, "mw_sk.hip")
 SK_DEPS = [SK_SRC, LIB_HOST, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_sk.h")]
 
 BOO_LIB = os.path.join(PKG, "libmw_boo.so")
 BOO_SRC = os.path.join(CSRC, "mw_boo.hip")
-BOO_DEPS = [BOO_SRC, LIB_HOST, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_boo.h")]
+BOO_DEPS = [BOO_SRC, LIB_HOST, LIB_CELLS, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_boo.h")]
 
 TET_LIB = os.path.join(PKG, "libmw_tet.so")
 TET_SRC = os.path.join(CSRC, "mw_tet.hip")
-TET_DEPS = [TET_SRC, LIB_HOST, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_tet.h")]
+TET_DEPS = [TET_SRC, LIB_HOST, LIB_CELLS, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_tet.h")]
 
 ADF_LIB = os.path.join(PKG, "libmw_adf.so")
 ADF_SRC = os.path.join(CSRC, "mw_adf.hip")
-ADF_DEPS = [ADF_SRC, LIB_HOST, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_adf.h")]
+ADF_DEPS = [ADF_SRC, LIB_HOST, LIB_CELLS, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_adf.h")]
 
 RINGS_LIB = os.path.join(PKG, "libmw_rings.so")
 RINGS_SRC = os.path.join(CSRC, "mw_rings.hip")
-RINGS_DEPS = [RINGS_SRC, LIB_HOST, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_rings.h")]
+RINGS_DEPS = [RINGS_SRC, LIB_HOST, LIB_CELLS, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_rings.h")]
 
 
 def hipcc_path():

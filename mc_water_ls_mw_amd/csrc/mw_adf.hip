@@ -1,13 +1,13 @@
 // libmw_adf.so -- the O-O-O angle distribution of include/mw_adf.h: for every centre molecule the angle between every two of
 // its (at most 32 kept) neighbour entries, binned in cos(theta) over the caller's edges into one integer histogram per box and
 // group, the entry counts of every molecule and four totals per box and group.  General geometry (nwater > 64): a counting
-// sort into a fractional cell grid (k_adf_bin, k_adf_scan, k_adf_place, k_adf_rank), then k_adf_angles, one lane per molecule
+// sort into a fractional cell grid (the sort of mw_lib_cells.h), then k_adf_angles, one lane per molecule
 // in sorted order, walks the 27 neighbouring cells.  Small geometry (nwater <= 64): k_adf_small, one wavefront per box with
 // the box in LDS.  In both a lane keeps an entry as (j, image) in LDS and forms its unit vector again when it pairs: the
 // first eight unit vectors of a lane live in registers, so a first-shell molecule (4 - 6 entries) forms each of its vectors
 // once and never looks at the other 24 slots.  The histograms of a workgroup are 32-bit counters in LDS, flushed with 64-bit
-// integer atomics; no floating-point number leaves the device.  (The binning kernels and the grid rules are those of
-// mw_tet.hip, written out again here: the libraries share host code only.)
+// integer atomics; no floating-point number leaves the device.  The grid rules, the sort and the two walks are
+// mw_lib_cells.h's, shared with libmw_boo.so, libmw_tet.so and the other libraries that sort into a cell grid.
 #include "../../include/mw_adf.h"
 
 #include "mw_common.hip.h"
@@ -18,59 +18,22 @@
 #pragma clang fp contract(off)
 
 #include "mw_lib_host.h"                       // after the pragma: its host arithmetic is uncontracted too
+#include "mw_lib_cells.h"
 
 namespace mwadf {
 
-constexpr int kThreads = 256;                     // the sorting kernels
+using namespace mwcells;
+
 constexpr int kPairThreads = 128;                 // k_adf_angles: 32 slots x 128 lanes x 4 bytes = 16 KiB of entries per workgroup
-constexpr int kSmallN = 64;
 constexpr int kKeep = MW_ADF_KEEP;
 constexpr int kRegs = 8;                          // unit vectors a lane holds in registers
 constexpr int kMaxBins = MW_ADF_MAX_BINS;
 constexpr int kMaxGroups = MW_ADF_MAX_GROUPS;
 constexpr int kSums = 4;                          // per box and group: centres, pairs enumerated, pairs binned, centres over the cap
-constexpr int kMaxGrid = 1024;
-constexpr int kMaxWater = 1 << 22;
-constexpr int kMaxBoxes = 1 << 24;
-constexpr int kMaxChunkBoxes = 65535;             // grid y
-constexpr int kSmallChunkBoxes = 1 << 20;
-constexpr double kGuard = 1.0 + 1e-9;
 constexpr int kPlaceBits = 22;                    // an entry: the place (or index) of j in the low bits, its image above
 constexpr int kPlaceMask = (1 << kPlaceBits) - 1;
 static_assert(kMaxWater <= (1 << kPlaceBits), "an entry holds a molecule in kPlaceBits bits");
 static_assert(kKeep * (kKeep - 1) / 2 * kThreads < (1LL << 31), "a workgroup's 32-bit counter holds every pair of its molecules");
-
-// s_a = (H^-1 r)_a reduced to [0, 1); I = H^-1, row-major
-__device__ __forceinline__ double frac_coord(const double* __restrict__ I, int a, double x, double y, double z)
-{
-    double s = __builtin_fma(I[3 * a], x, __builtin_fma(I[3 * a + 1], y, I[3 * a + 2] * z));
-    s = s - __builtin_floor(s);
-    return s >= 1.0 ? 0.0 : s;                 // (-1e-17 - floor = 1.0 after rounding)
-}
-
-// the cell of s along an axis of g cells, inside the table whatever s is
-__device__ __forceinline__ int cell_of(double s, int g)
-{
-    const int c = (int)(s * (double)g);
-    return c < 0 ? 0 : c >= g ? g - 1 : c;
-}
-
-// d = H ds (c = the cell's 9 doubles: c[3 k + a] = component a of h_(k+1)); returns |d|^2
-__device__ __forceinline__ double bond_vector(const double* __restrict__ c, double a0, double a1, double a2, double& dx, double& dy, double& dz)
-{
-    dx = __builtin_fma(c[0], a0, __builtin_fma(c[3], a1, c[6] * a2));
-    dy = __builtin_fma(c[1], a0, __builtin_fma(c[4], a1, c[7] * a2));
-    dz = __builtin_fma(c[2], a0, __builtin_fma(c[5], a1, c[8] * a2));
-    return __builtin_fma(dx, dx, __builtin_fma(dy, dy, dz * dz));
-}
-
-// Offset o in {-1, 0, 1} from cell c of g: the cell it lands in and the image shift that goes with it.
-__device__ __forceinline__ void wrap_cell(int c, int o, int g, int& cw, int& shift)
-{
-    cw = c + o; shift = 0;
-    if (cw < 0) { cw += g; shift = -1; }
-    if (cw >= g) { cw -= g; shift = 1; }
-}
 
 // ---- the LDS of a workgroup ------------------------------------------------------------------------------------------------
 // edges [nbins + 1] doubles | (small: the box, 3 x 64 doubles) | entries [kKeep][threads] ints | hist [ngroups][nbins] | sums [ngroups][4]
@@ -193,75 +156,6 @@ __device__ __forceinline__ void add_sums(unsigned* s, int n, int k, unsigned bin
 }
 
 // ---- general geometry ----------------------------------------------------------------------------------------------------
-// par[box][18]: the cell (9) and its inverse (9).  grid[box][4]: g_1, g_2, g_3, cells.  Per box in scratch: su [n][3] fractional
-// positions by index, cid [n], tmp [n] (members of the cells in arrival order), cnt / start [cap + 1]; then in cell order:
-// idx [n] the molecule, ss [n][3].
-
-// One lane per molecule: s, its cell, the cell's count.
-__global__ __launch_bounds__(kThreads) void k_adf_bin(int n, int cap, const double* __restrict__ par, const int* __restrict__ grid,
-                                                      const double* __restrict__ pos, double* __restrict__ su, int* __restrict__ cid,
-                                                      int* __restrict__ cnt)
-{
-    const int b = blockIdx.y, i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n) return;
-    const double* I = par + 18 * (size_t)b + 9;
-    const int* g = grid + 4 * (size_t)b;
-    const size_t m = (size_t)b * n + i;
-    const double x = pos[3 * m], y = pos[3 * m + 1], z = pos[3 * m + 2];
-    const double s0 = frac_coord(I, 0, x, y, z), s1 = frac_coord(I, 1, x, y, z), s2 = frac_coord(I, 2, x, y, z);
-    su[3 * m] = s0; su[3 * m + 1] = s1; su[3 * m + 2] = s2;
-    const int c = (cell_of(s2, g[2]) * g[1] + cell_of(s1, g[1])) * g[0] + cell_of(s0, g[0]);
-    cid[m] = c;
-    atomicAdd(cnt + (size_t)b * (cap + 1) + c, 1);
-}
-
-// One workgroup per box: start[c] = the members of the cells before c, start[cells] = n.
-__global__ __launch_bounds__(kThreads) void k_adf_scan(int cap, const int* __restrict__ grid, const int* __restrict__ cnt, int* __restrict__ start)
-{
-    __shared__ int part[kThreads];
-    const int b = blockIdx.x, tid = threadIdx.x, cells = grid[4 * (size_t)b + 3];
-    const int* cn = cnt + (size_t)b * (cap + 1);
-    int* st = start + (size_t)b * (cap + 1);
-    const int per = (cells + kThreads - 1) / kThreads, c0 = min(tid * per, cells), c1 = min(c0 + per, cells);
-    int sum = 0;
-    for (int c = c0; c < c1; ++c) sum += cn[c];
-    part[tid] = sum;
-    __syncthreads();
-    int before = 0;
-    for (int t = 0; t < tid; ++t) before += part[t];
-    for (int c = c0; c < c1; ++c) { st[c] = before; before += cn[c]; }
-    if (tid == kThreads - 1) st[cells] = before;
-}
-
-// One lane per molecule: a place among its cell's members, in arrival order (k_adf_rank puts them in index order).
-__global__ __launch_bounds__(kThreads) void k_adf_place(int n, int cap, const int* __restrict__ cid, const int* __restrict__ start,
-                                                        int* __restrict__ cnt, int* __restrict__ tmp)
-{
-    const int b = blockIdx.y, i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n) return;
-    const size_t m = (size_t)b * n + i, t = (size_t)b * (cap + 1);
-    const int c = cid[m];
-    const int slot = start[t + c] + atomicSub(cnt + t + c, 1) - 1;
-    tmp[(size_t)b * n + slot] = i;
-}
-
-// One lane per member: its rank by molecule index among the members of its cell is its place in the sorted order.
-__global__ __launch_bounds__(kThreads) void k_adf_rank(int n, int cap, const int* __restrict__ cid, const int* __restrict__ start,
-                                                       const int* __restrict__ tmp, const double* __restrict__ su, int* __restrict__ idx,
-                                                       double* __restrict__ ss)
-{
-    const int b = blockIdx.y, p = blockIdx.x * kThreads + threadIdx.x;
-    if (p >= n) return;
-    const size_t o = (size_t)b * n, t = (size_t)b * (cap + 1);
-    const int i = tmp[o + p], c = cid[o + i];
-    const int q0 = start[t + c], q1 = start[t + c + 1];
-    int rank = 0;
-    for (int q = q0; q < q1; ++q) rank += tmp[o + q] < i ? 1 : 0;
-    const size_t d = o + q0 + rank;
-    idx[d] = i;
-    ss[3 * d] = su[3 * (o + i)]; ss[3 * d + 1] = su[3 * (o + i) + 1]; ss[3 * d + 2] = su[3 * (o + i) + 2];
-}
-
 // The unit vector of an entry of the general geometry: the sorted place of j with the image shift (-1, 0, 1 per axis, base 3) above it.
 struct GeneralUnit {
     const double* H;
@@ -303,7 +197,7 @@ __global__ __launch_bounds__(kPairThreads) void k_adf_angles(int n, int cap, dou
     const int c0 = cell_of(s0, g0), c1 = cell_of(s1, g1), c2 = cell_of(s2, g2);
     int* ent = l.ent + tid;
     int cnt = 0;
-    if (active) {
+    if (active) {                                           // walk_cells' loops (mw_lib_cells.h), written out: on the template the pass was slower
         for (int oz = -1; oz <= 1; ++oz) {
             int wz, hz;
             wrap_cell(c2, oz, g2, wz, hz);
@@ -347,9 +241,7 @@ __global__ __launch_bounds__(kPairThreads) void k_adf_angles(int n, int cap, dou
 }
 
 // ---- small geometry: one wavefront per box, lane i = molecule i, the box's fractional positions in LDS ----------------------
-// The entries of i: j in index order, and for each j the eight combinations of ds_k and ds_k -/+ 1 (the only two images per
-// axis that can come within r_cut <= w_k), combination bit k choosing the second along axis k.  An entry is j with the
-// combination above it.
+// The entries of i in walk_small's order; an entry is j with the image combination above it.
 struct SmallUnit {
     const double* H;
     const double* S;
@@ -386,19 +278,10 @@ __global__ __launch_bounds__(64) void k_adf_small(int n, double rc2, const doubl
 
     int* ent = l.ent + lane;
     int cnt = 0;
-    for (int j = 0; j < n; ++j) {
-        const double e0 = S[j] - s0, e1 = S[64 + j] - s1, e2 = S[128 + j] - s2;
-        const double f0 = e0 > 0.0 ? e0 - 1.0 : e0 + 1.0, f1 = e1 > 0.0 ? e1 - 1.0 : e1 + 1.0, f2 = e2 > 0.0 ? e2 - 1.0 : e2 + 1.0;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            double dx, dy, dz;
-            const double r2 = bond_vector(H, (c & 1) ? f0 : e0, (c & 2) ? f1 : e1, (c & 4) ? f2 : e2, dx, dy, dz);
-            if (active && r2 < rc2 && r2 > 0.0) {
-                if (cnt < kKeep) ent[cnt * 64] = (c << kPlaceBits) | j;
-                ++cnt;
-            }
-        }
-    }
+    walk_small(n, active, rc2, H, S, s0, s1, s2, [&](int j, int c, double, double, double, double) {
+        if (cnt < kKeep) ent[cnt * 64] = (c << kPlaceBits) | j;
+        ++cnt;
+    });
     if (active && counts) counts[m] = cnt;
     if (pairs) {
         int gi = !active ? -1 : group ? group[m] : 0;
@@ -426,35 +309,22 @@ struct State : Runtime<4> {
     float ms[3] = {0.0f, 0.0f, 0.0f};
 } g;
 
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-// The scratch of one box of the general geometry, piece by piece (byte offsets inside a chunk are these times boxes per chunk).
-struct Layout {
-    int cap;                                                // cells a box may have
-    size_t su, cid, tmp, cnt, start, idx, ss, per_box;
+// The scratch of one box of the general geometry: the sort's pieces and nothing more.
+struct Layout : SortLayout {
+    size_t per_box;
 };
 
 Layout make_layout(int n)
 {
     Layout l;
-    l.cap = 2 * n > 64 ? 2 * n : 64;
-    const size_t tab = align16(4 * ((size_t)l.cap + 1));
     size_t o = 0;
-    l.su = o;    o += align16(24 * (size_t)n);
-    l.cid = o;   o += align16(4 * (size_t)n);
-    l.tmp = o;   o += align16(4 * (size_t)n);
-    l.cnt = o;   o += tab;
-    l.start = o; o += tab;
-    l.idx = o;   o += align16(4 * (size_t)n);
-    l.ss = o;    o += align16(24 * (size_t)n);
+    lay_sort(l, n, o);
     l.per_box = o;
     return l;
 }
 
-struct Plan {
-    int small, bpc, chunks, lds, boxes_per_wg;
+struct Plan : PlanBase {
     Layout lay;
-    size_t per_box;
 };
 
 // the histogram and the summary of a box
@@ -476,38 +346,6 @@ int make_plan(const char* who, int n, int nbins, int ngroups, int nboxes, size_t
     if (p.bpc > nboxes) p.bpc = nboxes;
     p.chunks = (nboxes + p.bpc - 1) / p.bpc;
     return 0;
-}
-
-void plan_fields(const Plan& p, const int grid[3], int* f)
-{
-    f[0] = p.bpc; f[1] = p.chunks; f[2] = p.small; f[3] = grid[0]; f[4] = grid[1]; f[5] = grid[2];
-    f[6] = p.lds; f[7] = (int)p.per_box; f[8] = p.boxes_per_wg;
-}
-
-// w_k = |det| / |h_l x h_m|
-void cell_widths(const double* c, double det, double w[3])
-{
-    for (int k = 0; k < 3; ++k) {
-        const double* a = c + 3 * ((k + 1) % 3);
-        const double* b = c + 3 * ((k + 2) % 3);
-        const double x = a[1] * b[2] - a[2] * b[1], y = a[2] * b[0] - a[0] * b[2], z = a[0] * b[1] - a[1] * b[0];
-        w[k] = std::fabs(det) / std::sqrt(x * x + y * y + z * z);
-    }
-}
-
-// g_k = max(1, floor(w_k / (r_cut (1 + 1e-9)))), each at most kMaxGrid, the largest lowered until the product fits `cap` cells
-void cell_grid(const double w[3], double rc, int cap, int g[3])
-{
-    for (int k = 0; k < 3; ++k) {
-        const double f = std::floor(w[k] / (rc * kGuard));
-        g[k] = f >= (double)kMaxGrid ? kMaxGrid : f >= 1.0 ? (int)f : 1;
-    }
-    while ((long long)g[0] * g[1] * g[2] > cap) {
-        int k = 0;
-        if (g[1] > g[k]) k = 1;
-        if (g[2] > g[k]) k = 2;
-        --g[k];
-    }
 }
 
 int check_scalars(const char* who, int nboxes, int n, double rc, int nbins, int ngroups)
@@ -547,30 +385,7 @@ int check_groups(const char* who, int nboxes, int n, int ngroups, const int* gro
     return 0;
 }
 
-// Every box's cell: invertible, and no narrower than r_cut (1 + 1e-9).  Fills par [nboxes][18] and grid [nboxes][4].
-int check_cells(const char* who, int nboxes, int n, const double* cells, double rc, std::vector<double>& par, std::vector<int>& grid)
-{
-    par.resize(18 * (size_t)nboxes);
-    grid.resize(4 * (size_t)nboxes);
-    const int cap = make_layout(n).cap;
-    for (int b = 0; b < nboxes; ++b) {
-        const double* c = cells + 9 * (size_t)b;
-        double* P = par.data() + 18 * (size_t)b;
-        double det, w[3];
-        if (!invert_cell(c, P + 9, &det))
-            return fail("%s: cells: the determinant of box %d is %g (zero or not finite)", who, b, det);
-        memcpy(P, c, 9 * sizeof(double));
-        cell_widths(c, det, w);
-        const double wmin = std::fmin(w[0], std::fmin(w[1], w[2]));
-        if (!(rc * kGuard <= wmin))
-            return fail("%s: r_cut = %.17g bohr is beyond the narrowest width %.17g bohr of box %d (r_cut (1 + 1e-9) <= every cell "
-                        "width is required)", who, rc, wmin, b);
-        int* G = grid.data() + 4 * (size_t)b;
-        cell_grid(w, rc, cap, G);
-        G[3] = G[0] * G[1] * G[2];
-    }
-    return 0;
-}
+const char kRadius[] = "r_cut";               // the radius the cells are checked against, in the messages
 
 // what both compute entries can check on the host before they look at the library's state
 int check_host_side(const char* who, int nboxes, int n, const double* cells, const double* pos, double rc, int nbins, const double* edges,
@@ -585,8 +400,6 @@ int check_host_side(const char* who, int nboxes, int n, const double* cells, con
 }
 
 int check_live(const char* who) { return check_live(who, "mw_adf_init", g); }
-
-dim3 per_molecule(int n, int nb, int threads) { return dim3((unsigned)((n + threads - 1) / threads), (unsigned)nb); }
 
 // The work of both entries, arguments already checked.  par, grid and edges are on the host; pos, group and the outputs are
 // device pointers when `dev`, host pointers otherwise.
@@ -644,30 +457,11 @@ int run(const char* who, int nboxes, int n, const std::vector<double>& par, cons
             HIPOK(hipGetLastError());
             HIPOK(hipEventRecord(g.ev[3], g.stream));
         } else {
-            char* base = (char*)g.scratch.p;
-            const size_t B = (size_t)p.bpc;
-            double* su = (double*)(base + l.su * B);
-            int* cid = (int*)(base + l.cid * B);
-            int* tmp = (int*)(base + l.tmp * B);
-            int* cnt = (int*)(base + l.cnt * B);
-            int* start = (int*)(base + l.start * B);
-            int* idx = (int*)(base + l.idx * B);
-            double* ss = (double*)(base + l.ss * B);
-            const dim3 grid_m = per_molecule(n, nb, kThreads);
-            HIPOK(hipMemsetAsync(cnt, 0, 4 * ((size_t)l.cap + 1) * nb, g.stream));
-            hipLaunchKernelGGL(k_adf_bin, grid_m, dim3(kThreads), 0, g.stream, n, l.cap, d_par, d_grid, d_pos, su, cid, cnt);
-            HIPOK(hipGetLastError());
-            hipLaunchKernelGGL(k_adf_scan, dim3((unsigned)nb), dim3(kThreads), 0, g.stream, l.cap, d_grid, (const int*)cnt, start);
-            HIPOK(hipGetLastError());
-            hipLaunchKernelGGL(k_adf_place, grid_m, dim3(kThreads), 0, g.stream, n, l.cap, (const int*)cid, (const int*)start, cnt, tmp);
-            HIPOK(hipGetLastError());
-            hipLaunchKernelGGL(k_adf_rank, grid_m, dim3(kThreads), 0, g.stream, n, l.cap, (const int*)cid, (const int*)start, (const int*)tmp,
-                               (const double*)su, idx, ss);
-            HIPOK(hipGetLastError());
+            Sorted s;
+            if (sort_into_cells(g.stream, n, nb, l, (char*)g.scratch.p, (size_t)p.bpc, d_par, d_grid, d_pos, s)) return 1;
             HIPOK(hipEventRecord(g.ev[2], g.stream));
             hipLaunchKernelGGL(k_adf_angles, per_molecule(n, nb, kPairThreads), dim3(kPairThreads), (size_t)p.lds, g.stream, n, l.cap, rc2, d_par,
-                               d_grid, (const int*)start, (const double*)ss, (const int*)idx, d_group, ngroups, nbins, pairs,
-                               (const double*)g.edges.p, d_hist, d_counts, d_sum);
+                               d_grid, s.start, s.ss, s.idx, d_group, ngroups, nbins, pairs, (const double*)g.edges.p, d_hist, d_counts, d_sum);
             HIPOK(hipGetLastError());
             HIPOK(hipEventRecord(g.ev[3], g.stream));
         }
@@ -716,7 +510,7 @@ int mw_adf_compute(int nboxes, int nwater, const double* cells, const double* po
     std::vector<double> par;
     std::vector<int> grid;
     if (check_host_side(who, nboxes, nwater, cells, pos, r_cut, nbins, edges, ngroups, group)) return 1;
-    if (check_cells(who, nboxes, nwater, cells, r_cut, par, grid)) return 1;
+    if (check_cells(who, kRadius, nboxes, nwater, cells, r_cut, par, grid)) return 1;
     if (group && check_groups(who, nboxes, nwater, ngroups, group)) return 1;
     if (check_live(who)) return 1;
     return run(who, nboxes, nwater, par, grid, pos, r_cut, nbins, edges, ngroups, group, false, hist, counts, summary);
@@ -732,10 +526,7 @@ int mw_adf_compute_device(int nboxes, int nwater, const double* cells, const dou
     if (check_live(who)) return 1;
     DeviceScope scope;
     HIPOK(scope.enter(g.device));
-    HIPOK(hipDeviceSynchronize());                            // whoever made the inputs (another stream, PyTorch's) is done
-    std::vector<double> h_cells(9 * (size_t)nboxes);
-    HIPOK(hipMemcpy(h_cells.data(), cells, h_cells.size() * sizeof(double), hipMemcpyDeviceToHost));
-    if (check_cells(who, nboxes, nwater, h_cells.data(), r_cut, par, grid)) return 1;
+    if (fetch_cells(who, kRadius, nboxes, nwater, cells, r_cut, par, grid)) return 1;
     if (group) {                                              // a value out of range must not reach the kernels
         std::vector<int> h_group((size_t)nboxes * nwater);
         HIPOK(hipMemcpy(h_group.data(), group, h_group.size() * sizeof(int), hipMemcpyDeviceToHost));
@@ -747,12 +538,9 @@ int mw_adf_compute_device(int nboxes, int nwater, const double* cells, const dou
 int mw_adf_plan(int nwater, const double* cell, double r_cut, int nbins, int ngroups, int nboxes, int* out, int nout)
 {
     const char* who = "mw_adf_plan";
-    std::vector<double> par;
     std::vector<int> grid;
     if (check_scalars(who, nboxes, nwater, r_cut, nbins, ngroups)) return 1;
-    if (!cell) return fail("%s: cell is NULL", who);
-    if (!out || nout < 1) return fail("%s: out is NULL or nout < 1", who);
-    if (check_cells(who, 1, nwater, cell, r_cut, par, grid)) return 1;
+    if (plan_grid(who, kRadius, nwater, cell, r_cut, out, nout, grid)) return 1;
     Plan p;
     if (make_plan(who, nwater, nbins, ngroups, nboxes, g.live ? g.budget : kDefaultBudget, p)) return 1;
     int f[MW_ADF_PLAN_FIELDS];
@@ -761,14 +549,7 @@ int mw_adf_plan(int nwater, const double* cell, double r_cut, int nbins, int ngr
     return 0;
 }
 
-int mw_adf_last(int* out, int nout)
-{
-    if (check_live("mw_adf_last")) return 1;
-    if (!out || nout < 1) return fail("mw_adf_last: out is NULL or nout < 1");
-    if (!g.have_last) return fail("mw_adf_last: no call has launched yet");
-    copy_fields(g.last, MW_ADF_PLAN_FIELDS, out, nout);
-    return 0;
-}
+int mw_adf_last(int* out, int nout) { return last_fields("mw_adf_last", "mw_adf_init", g, g.last, MW_ADF_PLAN_FIELDS, out, nout); }
 
 int mw_adf_elapsed_ms(float* binning, float* angles, float* reduce)
 {

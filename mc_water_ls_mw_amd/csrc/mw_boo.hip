@@ -1,10 +1,11 @@
 // libmw_boo.so -- the Steinhardt bond-order parameters of include/mw_boo.h: q4, q6, their neighbour averages, the solid-like
 // connection count of every molecule and the box summary (Q4, Q6, <qbar4>, <qbar6>), for many boxes.  General geometry
-// (nwater > 64): a counting sort into a fractional cell grid (k_boo_bin, k_boo_scan, k_boo_place, k_boo_rank), then one
+// (nwater > 64): a counting sort into a fractional cell grid (the sort of mw_lib_cells.h), then one
 // lane per molecule in sorted order walks the 27 neighbouring cells twice -- k_boo_pass1 for n_i and the 22 harmonic sums,
 // k_boo_pass2 for the neighbours' vectors -- and k_boo_summary adds the box up.  Small geometry (nwater <= 64): k_boo_small,
 // one wavefront per box with the box in LDS.  Every bit of a box's results depends on the box, rc and the threshold alone
 // (mw_boo.h): the arithmetic below is spelled out in fma / mul / add with contraction off, and the order of every sum is fixed.
+// The grid rules, the sort and the two walks are mw_lib_cells.h's, shared with the other libraries that sort into a cell grid.
 #include "../../include/mw_boo.h"
 
 #include "mw_common.hip.h"
@@ -15,21 +16,16 @@
 #pragma clang fp contract(off)
 
 #include "mw_lib_host.h"                       // after the pragma: its host arithmetic is uncontracted too
+#include "mw_lib_cells.h"
 
 namespace mwboo {
 
-constexpr int kThreads = 256;
-constexpr int kSmallN = 64;
+using namespace mwcells;
+
 constexpr int kSmallBoxesPerWg = kThreads / 64;   // one wavefront per box
 constexpr int kNY = 22;                           // 9 components of l = 4, then 13 of l = 6
 constexpr int kRec = 24;                          // doubles per molecule in scratch: q_lm, |q_6|, n_i
 constexpr int kSums = 25;                         // box sums: 22 of n_i q_lm, sum n_i, sum qbar4, sum qbar6
-constexpr int kMaxGrid = 1024;
-constexpr int kMaxWater = 1 << 22;
-constexpr int kMaxBoxes = 1 << 24;
-constexpr int kMaxChunkBoxes = 65535;             // grid y
-constexpr int kSmallChunkBoxes = 1 << 20;
-constexpr double kGuard = 1.0 + 1e-9;
 constexpr int kSmallLds = kSmallBoxesPerWg * (3 + kRec) * 64 * 8;
 
 // c_lm = sqrt((2 - delta_m0) (l - m)! / (l + m)!)
@@ -69,30 +65,6 @@ __device__ __forceinline__ void harmonics(double x, double y, double z, double (
     Y[20] = (10395.0 * k66) * c6; Y[21] = (10395.0 * k66) * s6;
 }
 
-// s_a = (H^-1 r)_a reduced to [0, 1); I = H^-1, row-major
-__device__ __forceinline__ double frac_coord(const double* __restrict__ I, int a, double x, double y, double z)
-{
-    double s = __builtin_fma(I[3 * a], x, __builtin_fma(I[3 * a + 1], y, I[3 * a + 2] * z));
-    s = s - __builtin_floor(s);
-    return s >= 1.0 ? 0.0 : s;                 // (-1e-17 - floor = 1.0 after rounding)
-}
-
-// the cell of s along an axis of g cells, inside the table whatever s is
-__device__ __forceinline__ int cell_of(double s, int g)
-{
-    const int c = (int)(s * (double)g);
-    return c < 0 ? 0 : c >= g ? g - 1 : c;
-}
-
-// d = H ds (c = the cell's 9 doubles: c[3 k + a] = component a of h_(k+1)); returns |d|^2
-__device__ __forceinline__ double bond_vector(const double* __restrict__ c, double a0, double a1, double a2, double& dx, double& dy, double& dz)
-{
-    dx = __builtin_fma(c[0], a0, __builtin_fma(c[3], a1, c[6] * a2));
-    dy = __builtin_fma(c[1], a0, __builtin_fma(c[4], a1, c[7] * a2));
-    dz = __builtin_fma(c[2], a0, __builtin_fma(c[5], a1, c[8] * a2));
-    return __builtin_fma(dx, dx, __builtin_fma(dy, dy, dz * dz));
-}
-
 __device__ __forceinline__ void unit_harmonics(double r2, double dx, double dy, double dz, double (&Y)[kNY])
 {
     const double rinv = 1.0 / __builtin_sqrt(r2);
@@ -106,114 +78,8 @@ __device__ __forceinline__ double norm_of(const double* v, int first, int count)
     return __builtin_sqrt(s);
 }
 
-// Offset o in {-1, 0, 1} from cell c of g: the cell it lands in and the image shift that goes with it.
-__device__ __forceinline__ void wrap_cell(int c, int o, int g, int& cw, double& shift)
-{
-    cw = c + o; shift = 0.0;
-    if (cw < 0) { cw += g; shift = -1.0; }
-    if (cw >= g) { cw -= g; shift = 1.0; }
-}
-
 // ---- general geometry ----------------------------------------------------------------------------------------------------
-// par[box][18]: the cell (9) and its inverse (9).  grid[box][4]: g_1, g_2, g_3, cells.  Per box in scratch: su [n][3] fractional
-// positions by index, cid [n], tmp [n] (members of the cells in arrival order), cnt / start [cap + 1]; then in cell order:
-// idx [n] the molecule, ss [n][3], rec [n][kRec], qbar [n][2].
-
-// One lane per molecule: s, its cell, the cell's count.
-__global__ __launch_bounds__(kThreads) void k_boo_bin(int n, int cap, const double* __restrict__ par, const int* __restrict__ grid,
-                                                      const double* __restrict__ pos, double* __restrict__ su, int* __restrict__ cid,
-                                                      int* __restrict__ cnt)
-{
-    const int b = blockIdx.y, i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n) return;
-    const double* I = par + 18 * (size_t)b + 9;
-    const int* g = grid + 4 * (size_t)b;
-    const size_t m = (size_t)b * n + i;
-    const double x = pos[3 * m], y = pos[3 * m + 1], z = pos[3 * m + 2];
-    const double s0 = frac_coord(I, 0, x, y, z), s1 = frac_coord(I, 1, x, y, z), s2 = frac_coord(I, 2, x, y, z);
-    su[3 * m] = s0; su[3 * m + 1] = s1; su[3 * m + 2] = s2;
-    const int c = (cell_of(s2, g[2]) * g[1] + cell_of(s1, g[1])) * g[0] + cell_of(s0, g[0]);
-    cid[m] = c;
-    atomicAdd(cnt + (size_t)b * (cap + 1) + c, 1);
-}
-
-// One workgroup per box: start[c] = the members of the cells before c, start[cells] = n.
-__global__ __launch_bounds__(kThreads) void k_boo_scan(int cap, const int* __restrict__ grid, const int* __restrict__ cnt, int* __restrict__ start)
-{
-    __shared__ int part[kThreads];
-    const int b = blockIdx.x, tid = threadIdx.x, cells = grid[4 * (size_t)b + 3];
-    const int* cn = cnt + (size_t)b * (cap + 1);
-    int* st = start + (size_t)b * (cap + 1);
-    const int per = (cells + kThreads - 1) / kThreads, c0 = min(tid * per, cells), c1 = min(c0 + per, cells);
-    int sum = 0;
-    for (int c = c0; c < c1; ++c) sum += cn[c];
-    part[tid] = sum;
-    __syncthreads();
-    int before = 0;
-    for (int t = 0; t < tid; ++t) before += part[t];
-    for (int c = c0; c < c1; ++c) { st[c] = before; before += cn[c]; }
-    if (tid == kThreads - 1) st[cells] = before;
-}
-
-// One lane per molecule: a place among its cell's members, in arrival order (k_boo_rank puts them in index order).
-__global__ __launch_bounds__(kThreads) void k_boo_place(int n, int cap, const int* __restrict__ cid, const int* __restrict__ start,
-                                                        int* __restrict__ cnt, int* __restrict__ tmp)
-{
-    const int b = blockIdx.y, i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n) return;
-    const size_t m = (size_t)b * n + i, t = (size_t)b * (cap + 1);
-    const int c = cid[m];
-    const int slot = start[t + c] + atomicSub(cnt + t + c, 1) - 1;
-    tmp[(size_t)b * n + slot] = i;
-}
-
-// One lane per member: its rank by molecule index among the members of its cell is its place in the sorted order.
-__global__ __launch_bounds__(kThreads) void k_boo_rank(int n, int cap, const int* __restrict__ cid, const int* __restrict__ start,
-                                                       const int* __restrict__ tmp, const double* __restrict__ su, int* __restrict__ idx,
-                                                       double* __restrict__ ss)
-{
-    const int b = blockIdx.y, p = blockIdx.x * kThreads + threadIdx.x;
-    if (p >= n) return;
-    const size_t o = (size_t)b * n, t = (size_t)b * (cap + 1);
-    const int i = tmp[o + p], c = cid[o + i];
-    const int q0 = start[t + c], q1 = start[t + c + 1];
-    int rank = 0;
-    for (int q = q0; q < q1; ++q) rank += tmp[o + q] < i ? 1 : 0;
-    const size_t d = o + q0 + rank;
-    idx[d] = i;
-    ss[3 * d] = su[3 * (o + i)]; ss[3 * d + 1] = su[3 * (o + i) + 1]; ss[3 * d + 2] = su[3 * (o + i) + 2];
-}
-
-// The walk both passes share: calls hit(q, r2, dx, dy, dz) for every entry of the molecule at sorted place p, in the
-// contract's order.
-template <typename Hit>
-__device__ __forceinline__ void walk_cells(int p, double rc2, const double* __restrict__ H, const int* __restrict__ g, const int* __restrict__ st,
-                                           const double* __restrict__ S, Hit hit)
-{
-    const double s0 = S[3 * (size_t)p], s1 = S[3 * (size_t)p + 1], s2 = S[3 * (size_t)p + 2];
-    const int g0 = g[0], g1 = g[1], g2 = g[2];
-    const int c0 = cell_of(s0, g0), c1 = cell_of(s1, g1), c2 = cell_of(s2, g2);
-    for (int oz = -1; oz <= 1; ++oz) {
-        int wz; double hz;
-        wrap_cell(c2, oz, g2, wz, hz);
-        for (int oy = -1; oy <= 1; ++oy) {
-            int wy; double hy;
-            wrap_cell(c1, oy, g1, wy, hy);
-            for (int ox = -1; ox <= 1; ++ox) {
-                int wx; double hx;
-                wrap_cell(c0, ox, g0, wx, hx);
-                const int c = (wz * g1 + wy) * g0 + wx;
-                const int q1 = st[c + 1];
-                for (int q = st[c]; q < q1; ++q) {
-                    const double a0 = (S[3 * (size_t)q] - s0) + hx, a1 = (S[3 * (size_t)q + 1] - s1) + hy, a2 = (S[3 * (size_t)q + 2] - s2) + hz;
-                    double dx, dy, dz;
-                    const double r2 = bond_vector(H, a0, a1, a2, dx, dy, dz);
-                    if (r2 < rc2 && r2 > 0.0) hit(q, r2, dx, dy, dz);
-                }
-            }
-        }
-    }
-}
+// Per box in scratch after the sort's pieces (mw_lib_cells.h), in cell order: rec [n][kRec], qbar [n][2].
 
 // Pass 1, one lane per molecule in sorted order: n_i and q_lm(i) into rec.
 __global__ __launch_bounds__(kThreads) void k_boo_pass1(int n, int cap, double rc2, const double* __restrict__ par, const int* __restrict__ grid,
@@ -225,8 +91,10 @@ __global__ __launch_bounds__(kThreads) void k_boo_pass1(int n, int cap, double r
 #pragma unroll
     for (int k = 0; k < kNY; ++k) acc[k] = 0.0;
     int cnt = 0;
-    walk_cells(p, rc2, par + 18 * (size_t)b, grid + 4 * (size_t)b, start + (size_t)b * (cap + 1), ss + 3 * (size_t)b * n,
-               [&](int, double r2, double dx, double dy, double dz) {
+    const double* S = ss + 3 * (size_t)b * n;
+    walk_cells(S[3 * (size_t)p], S[3 * (size_t)p + 1], S[3 * (size_t)p + 2], rc2, par + 18 * (size_t)b, grid + 4 * (size_t)b,
+               start + (size_t)b * (cap + 1), S,
+               [&](int, int, int, int, double r2, double dx, double dy, double dz) {
                    double Y[kNY];
                    unit_harmonics(r2, dx, dy, dz, Y);
 #pragma unroll
@@ -259,8 +127,10 @@ __global__ __launch_bounds__(kThreads) void k_boo_pass2(int n, int cap, double r
 #pragma unroll
     for (int k = 0; k < kNY; ++k) bar[k] = own[k];
     int conn = 0;
-    walk_cells(p, rc2, par + 18 * (size_t)b, grid + 4 * (size_t)b, start + (size_t)b * (cap + 1), ss + 3 * (size_t)b * n,
-               [&](int j, double, double, double, double) {
+    const double* S = ss + 3 * (size_t)b * n;
+    walk_cells(S[3 * (size_t)p], S[3 * (size_t)p + 1], S[3 * (size_t)p + 2], rc2, par + 18 * (size_t)b, grid + 4 * (size_t)b,
+               start + (size_t)b * (cap + 1), S,
+               [&](int j, int, int, int, double, double, double, double) {
                    const double* rj = R + kRec * (size_t)j;
                    double dot = 0.0;
 #pragma unroll
@@ -330,24 +200,6 @@ __global__ __launch_bounds__(kThreads) void k_boo_summary(int n, const double* _
 }
 
 // ---- small geometry: one wavefront per box, lane i = molecule i, the box's fractional positions and records in LDS ---------
-// The entries of i: j in index order, and for each j the eight combinations of ds_k and ds_k -/+ 1 (the only two images per
-// axis that can come within rc <= w_k), combination bit k choosing the second along axis k.
-template <typename Hit>
-__device__ __forceinline__ void walk_small(int n, bool active, double rc2, const double* __restrict__ H, const double* S, double s0, double s1,
-                                           double s2, Hit hit)
-{
-    for (int j = 0; j < n; ++j) {
-        const double e0 = S[j] - s0, e1 = S[64 + j] - s1, e2 = S[128 + j] - s2;
-        const double f0 = e0 > 0.0 ? e0 - 1.0 : e0 + 1.0, f1 = e1 > 0.0 ? e1 - 1.0 : e1 + 1.0, f2 = e2 > 0.0 ? e2 - 1.0 : e2 + 1.0;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            double dx, dy, dz;
-            const double r2 = bond_vector(H, (c & 1) ? f0 : e0, (c & 2) ? f1 : e1, (c & 4) ? f2 : e2, dx, dy, dz);
-            if (active && r2 < rc2 && r2 > 0.0) hit(j, r2, dx, dy, dz);
-        }
-    }
-}
-
 __global__ __launch_bounds__(kThreads) void k_boo_small(int nb, int n, double rc2, double thr, const double* __restrict__ par,
                                                         const double* __restrict__ pos, double* __restrict__ q, int* __restrict__ nn,
                                                         double* __restrict__ summary)
@@ -371,7 +223,7 @@ __global__ __launch_bounds__(kThreads) void k_boo_small(int nb, int n, double rc
 #pragma unroll
     for (int k = 0; k < kNY; ++k) own[k] = 0.0;
     int cnt = 0;
-    walk_small(n, active, rc2, H, S, s0, s1, s2, [&](int, double r2, double dx, double dy, double dz) {
+    walk_small(n, active, rc2, H, S, s0, s1, s2, [&](int, int, double r2, double dx, double dy, double dz) {
         double Y[kNY];
         unit_harmonics(r2, dx, dy, dz, Y);
 #pragma unroll
@@ -391,7 +243,7 @@ __global__ __launch_bounds__(kThreads) void k_boo_small(int nb, int n, double rc
 #pragma unroll
     for (int k = 0; k < kNY; ++k) bar[k] = own[k];
     int conn = 0;
-    walk_small(n, active, rc2, H, S, s0, s1, s2, [&](int j, double, double, double, double) {
+    walk_small(n, active, rc2, H, S, s0, s1, s2, [&](int j, int, double, double, double, double) {
         double dot = 0.0;
 #pragma unroll
         for (int k = 0; k < kNY; ++k) {
@@ -433,37 +285,24 @@ struct State : Runtime<5> {
     float ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 } g;
 
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-// The scratch of one box of the general geometry, piece by piece (byte offsets inside a chunk are these times boxes per chunk).
-struct Layout {
-    int cap;                                                // cells a box may have
-    size_t su, cid, tmp, cnt, start, idx, ss, rec, qbar, per_box;
+// The scratch of one box of the general geometry: the sort's pieces, then rec and qbar.
+struct Layout : SortLayout {
+    size_t rec, qbar, per_box;
 };
 
 Layout make_layout(int n)
 {
     Layout l;
-    l.cap = 2 * n > 64 ? 2 * n : 64;
-    const size_t tab = align16(4 * ((size_t)l.cap + 1));
     size_t o = 0;
-    l.su = o;    o += align16(24 * (size_t)n);
-    l.cid = o;   o += align16(4 * (size_t)n);
-    l.tmp = o;   o += align16(4 * (size_t)n);
-    l.cnt = o;   o += tab;
-    l.start = o; o += tab;
-    l.idx = o;   o += align16(4 * (size_t)n);
-    l.ss = o;    o += align16(24 * (size_t)n);
+    lay_sort(l, n, o);
     l.rec = o;   o += align16(8 * (size_t)kRec * n);
     l.qbar = o;  o += align16(16 * (size_t)n);
     l.per_box = o;
     return l;
 }
 
-struct Plan {
-    int small, bpc, chunks, lds, boxes_per_wg;
+struct Plan : PlanBase {
     Layout lay;
-    size_t per_box;
 };
 
 int make_plan(const char* who, int n, int nboxes, size_t budget, Plan& p)
@@ -486,38 +325,6 @@ int make_plan(const char* who, int n, int nboxes, size_t budget, Plan& p)
     return 0;
 }
 
-void plan_fields(const Plan& p, const int grid[3], int* f)
-{
-    f[0] = p.bpc; f[1] = p.chunks; f[2] = p.small; f[3] = grid[0]; f[4] = grid[1]; f[5] = grid[2];
-    f[6] = p.lds; f[7] = (int)p.per_box; f[8] = p.boxes_per_wg;
-}
-
-// w_k = |det| / |h_l x h_m|
-void cell_widths(const double* c, double det, double w[3])
-{
-    for (int k = 0; k < 3; ++k) {
-        const double* a = c + 3 * ((k + 1) % 3);
-        const double* b = c + 3 * ((k + 2) % 3);
-        const double x = a[1] * b[2] - a[2] * b[1], y = a[2] * b[0] - a[0] * b[2], z = a[0] * b[1] - a[1] * b[0];
-        w[k] = std::fabs(det) / std::sqrt(x * x + y * y + z * z);
-    }
-}
-
-// g_k = max(1, floor(w_k / (rc (1 + 1e-9)))), each at most kMaxGrid, the largest lowered until the product fits `cap` cells
-void cell_grid(const double w[3], double rc, int cap, int g[3])
-{
-    for (int k = 0; k < 3; ++k) {
-        const double f = std::floor(w[k] / (rc * kGuard));
-        g[k] = f >= (double)kMaxGrid ? kMaxGrid : f >= 1.0 ? (int)f : 1;
-    }
-    while ((long long)g[0] * g[1] * g[2] > cap) {
-        int k = 0;
-        if (g[1] > g[k]) k = 1;
-        if (g[2] > g[k]) k = 2;
-        --g[k];
-    }
-}
-
 int check_scalars(const char* who, int nboxes, int n, double rc, double threshold)
 {
     if (nboxes < 1 || nboxes > kMaxBoxes) return fail("%s: nboxes = %d outside 1..%d", who, nboxes, kMaxBoxes);
@@ -527,34 +334,9 @@ int check_scalars(const char* who, int nboxes, int n, double rc, double threshol
     return 0;
 }
 
-// Every box's cell: invertible, and no narrower than rc (1 + 1e-9).  Fills par [nboxes][18] and grid [nboxes][4].
-int check_cells(const char* who, int nboxes, int n, const double* cells, double rc, std::vector<double>& par, std::vector<int>& grid)
-{
-    par.resize(18 * (size_t)nboxes);
-    grid.resize(4 * (size_t)nboxes);
-    const int cap = make_layout(n).cap;
-    for (int b = 0; b < nboxes; ++b) {
-        const double* c = cells + 9 * (size_t)b;
-        double* P = par.data() + 18 * (size_t)b;
-        double det, w[3];
-        if (!invert_cell(c, P + 9, &det))
-            return fail("%s: cells: the determinant of box %d is %g (zero or not finite)", who, b, det);
-        memcpy(P, c, 9 * sizeof(double));
-        cell_widths(c, det, w);
-        const double wmin = std::fmin(w[0], std::fmin(w[1], w[2]));
-        if (!(rc * kGuard <= wmin))
-            return fail("%s: rc = %.17g bohr is beyond the narrowest width %.17g bohr of box %d (rc (1 + 1e-9) <= every cell width is required)",
-                        who, rc, wmin, b);
-        int* G = grid.data() + 4 * (size_t)b;
-        cell_grid(w, rc, cap, G);
-        G[3] = G[0] * G[1] * G[2];
-    }
-    return 0;
-}
+const char kRadius[] = "rc";                  // the radius the cells are checked against, in the messages
 
 int check_live(const char* who) { return check_live(who, "mw_boo_init", g); }
-
-dim3 per_molecule(int n, int nb) { return dim3((unsigned)((n + kThreads - 1) / kThreads), (unsigned)nb); }
 
 // The work of both entries, arguments already checked.  par and grid are on the host; pos and the outputs are device pointers
 // when `dev`, host pointers otherwise.
@@ -602,33 +384,18 @@ int run(const char* who, int nboxes, int n, const std::vector<double>& par, cons
             if (!d_sum) d_sum = (double*)g.summary.p;
             char* base = (char*)g.scratch.p;
             const size_t B = (size_t)p.bpc;
-            double* su = (double*)(base + l.su * B);
-            int* cid = (int*)(base + l.cid * B);
-            int* tmp = (int*)(base + l.tmp * B);
-            int* cnt = (int*)(base + l.cnt * B);
-            int* start = (int*)(base + l.start * B);
-            int* idx = (int*)(base + l.idx * B);
-            double* ss = (double*)(base + l.ss * B);
             double* rec = (double*)(base + l.rec * B);
             double* qbar = (double*)(base + l.qbar * B);
             const dim3 grid_m = per_molecule(n, nb);
+            Sorted s;
             HIPOK(hipEventRecord(g.ev[0], g.stream));
-            HIPOK(hipMemsetAsync(cnt, 0, 4 * ((size_t)l.cap + 1) * nb, g.stream));
-            hipLaunchKernelGGL(k_boo_bin, grid_m, dim3(kThreads), 0, g.stream, n, l.cap, d_par, d_grid, d_pos, su, cid, cnt);
-            HIPOK(hipGetLastError());
-            hipLaunchKernelGGL(k_boo_scan, dim3((unsigned)nb), dim3(kThreads), 0, g.stream, l.cap, d_grid, (const int*)cnt, start);
-            HIPOK(hipGetLastError());
-            hipLaunchKernelGGL(k_boo_place, grid_m, dim3(kThreads), 0, g.stream, n, l.cap, (const int*)cid, (const int*)start, cnt, tmp);
-            HIPOK(hipGetLastError());
-            hipLaunchKernelGGL(k_boo_rank, grid_m, dim3(kThreads), 0, g.stream, n, l.cap, (const int*)cid, (const int*)start, (const int*)tmp,
-                               (const double*)su, idx, ss);
-            HIPOK(hipGetLastError());
+            if (sort_into_cells(g.stream, n, nb, l, base, B, d_par, d_grid, d_pos, s)) return 1;
             HIPOK(hipEventRecord(g.ev[1], g.stream));
-            hipLaunchKernelGGL(k_boo_pass1, grid_m, dim3(kThreads), 0, g.stream, n, l.cap, rc2, d_par, d_grid, (const int*)start, (const double*)ss, rec);
+            hipLaunchKernelGGL(k_boo_pass1, grid_m, dim3(kThreads), 0, g.stream, n, l.cap, rc2, d_par, d_grid, s.start, s.ss, rec);
             HIPOK(hipGetLastError());
             HIPOK(hipEventRecord(g.ev[2], g.stream));
-            hipLaunchKernelGGL(k_boo_pass2, grid_m, dim3(kThreads), 0, g.stream, n, l.cap, rc2, thr, d_par, d_grid, (const int*)start, (const double*)ss,
-                               (const int*)idx, (const double*)rec, qbar, d_q, d_nn);
+            hipLaunchKernelGGL(k_boo_pass2, grid_m, dim3(kThreads), 0, g.stream, n, l.cap, rc2, thr, d_par, d_grid, s.start, s.ss, s.idx,
+                               (const double*)rec, qbar, d_q, d_nn);
             HIPOK(hipGetLastError());
             HIPOK(hipEventRecord(g.ev[3], g.stream));
             hipLaunchKernelGGL(k_boo_summary, dim3((unsigned)nb), dim3(kThreads), 0, g.stream, n, (const double*)rec, (const double*)qbar, d_sum);
@@ -684,7 +451,7 @@ int mw_boo_compute(int nboxes, int nwater, const double* cells, const double* po
     if (check_scalars(who, nboxes, nwater, rc, threshold)) return 1;
     if (!cells) return fail("%s: cells is NULL", who);
     if (!pos) return fail("%s: pos is NULL", who);
-    if (check_cells(who, nboxes, nwater, cells, rc, par, grid)) return 1;
+    if (check_cells(who, kRadius, nboxes, nwater, cells, rc, par, grid)) return 1;
     if (check_live(who)) return 1;
     return run(who, nboxes, nwater, par, grid, pos, rc, threshold, false, q, nn, summary);
 }
@@ -701,22 +468,16 @@ int mw_boo_compute_device(int nboxes, int nwater, const double* cells, const dou
     if (check_live(who)) return 1;
     DeviceScope scope;
     HIPOK(scope.enter(g.device));
-    HIPOK(hipDeviceSynchronize());                            // whoever made the inputs (another stream, PyTorch's) is done
-    std::vector<double> h_cells(9 * (size_t)nboxes);
-    HIPOK(hipMemcpy(h_cells.data(), cells, h_cells.size() * sizeof(double), hipMemcpyDeviceToHost));
-    if (check_cells(who, nboxes, nwater, h_cells.data(), rc, par, grid)) return 1;
+    if (fetch_cells(who, kRadius, nboxes, nwater, cells, rc, par, grid)) return 1;
     return run(who, nboxes, nwater, par, grid, pos, rc, threshold, true, q, nn, summary);
 }
 
 int mw_boo_plan(int nwater, const double* cell, double rc, int nboxes, int* out, int nout)
 {
     const char* who = "mw_boo_plan";
-    std::vector<double> par;
     std::vector<int> grid;
     if (check_scalars(who, nboxes, nwater, rc, 0.0)) return 1;
-    if (!cell) return fail("%s: cell is NULL", who);
-    if (!out || nout < 1) return fail("%s: out is NULL or nout < 1", who);
-    if (check_cells(who, 1, nwater, cell, rc, par, grid)) return 1;
+    if (plan_grid(who, kRadius, nwater, cell, rc, out, nout, grid)) return 1;
     Plan p;
     if (make_plan(who, nwater, nboxes, g.live ? g.budget : kDefaultBudget, p)) return 1;
     int f[MW_BOO_PLAN_FIELDS];
@@ -725,14 +486,7 @@ int mw_boo_plan(int nwater, const double* cell, double rc, int nboxes, int* out,
     return 0;
 }
 
-int mw_boo_last(int* out, int nout)
-{
-    if (check_live("mw_boo_last")) return 1;
-    if (!out || nout < 1) return fail("mw_boo_last: out is NULL or nout < 1");
-    if (!g.have_last) return fail("mw_boo_last: no call has launched yet");
-    copy_fields(g.last, MW_BOO_PLAN_FIELDS, out, nout);
-    return 0;
-}
+int mw_boo_last(int* out, int nout) { return last_fields("mw_boo_last", "mw_boo_init", g, g.last, MW_BOO_PLAN_FIELDS, out, nout); }
 
 int mw_boo_elapsed_ms(float* binning, float* pass1, float* pass2, float* summary)
 {

@@ -1,15 +1,15 @@
 // libmw_rings.so -- the primitive rings of include/mw_rings.h: for every box the closed paths of 3 to 7 nodes of the bond
 // network over (molecule, image) nodes, counted once per cell at their smallest reading, and those of them that are shortest
 // paths; per size the histogram, the membership of every molecule and, on request, the list.  The entries of a molecule are
-// found as libmw_adf.so finds them -- general geometry (nwater > 64): a counting sort into a fractional cell grid (k_ring_bin,
-// k_ring_scan, k_ring_place, k_ring_rank), then k_ring_adj, one lane per molecule over the 27 neighbouring cells; small
-// geometry (nwater <= 64): k_ring_small, one wavefront per box with the box in LDS -- and go to scratch as n_i and the first 8
-// packed (molecule, image) codes.  k_ring_rows sorts every row and drops what touches a molecule over the cap.  k_ring_walk,
+// found as libmw_adf.so finds them -- general geometry (nwater > 64): a counting sort into a fractional cell grid (the sort
+// of mw_lib_cells.h), then k_ring_adj, one lane per molecule over the 27 neighbouring cells; small geometry (nwater <= 64):
+// k_ring_small, one wavefront per box with the box in LDS -- and go to scratch as n_i and the first 8 packed (molecule, image)
+// codes.  k_ring_rows sorts every row and drops what touches a molecule over the cap.  k_ring_walk,
 // one lane per (root, first edge), runs the depth-first walk on a stack in LDS, reads the rows of other molecules from
 // scratch, applies the canonical and the shortest-path test at closure and keeps the workgroup's counters in LDS, flushed
 // with 64-bit integer atomics.  The list takes k_ring_offsets (a scan of the per-lane ring counts) and the walk again.  No
-// floating-point number leaves the device.  (The binning kernels and the grid rules are those of mw_adf.hip, written out
-// again here: the libraries share host code only.)
+// floating-point number leaves the device.  The grid rules, the sort and the device primitives are mw_lib_cells.h's, shared
+// with libmw_boo.so, libmw_tet.so and libmw_adf.so.
 #include "../../include/mw_rings.h"
 
 #include "mw_common.hip.h"
@@ -20,21 +20,17 @@
 #pragma clang fp contract(off)
 
 #include "mw_lib_host.h"                       // after the pragma: its host arithmetic is uncontracted too
+#include "mw_lib_cells.h"
 
 namespace mwrings {
 
-constexpr int kThreads = 256;                     // the sorting kernels, k_ring_adj, k_ring_rows, k_ring_offsets
+using namespace mwcells;                          // kThreads: the sorting kernels, k_ring_adj, k_ring_rows, k_ring_offsets
+
 constexpr int kWalkThreads = 128;                 // k_ring_walk: a stack of 7 levels x 2 ints per lane = 7 KiB of LDS
-constexpr int kSmallN = 64;
 constexpr int kDeg = MW_RINGS_DEG;
 constexpr int kSizes = MW_RINGS_SIZES;
 constexpr int kMaxRing = MW_RINGS_MAX;
 constexpr int kSums = 4;
-constexpr int kMaxGrid = 1024;
-constexpr int kMaxWater = 1 << 22;
-constexpr int kMaxBoxes = 1 << 24;
-constexpr int kMaxChunkBoxes = 65535;             // grid y
-constexpr double kGuard = 1.0 + 1e-9;
 // A code: the molecule j above six bits of image, (n_1 + 1) (n_2 + 1) (n_3 + 1) two bits each, so that codes ascend as
 // (j, n_1, n_2, n_3) does.  kEmpty pads a row.
 constexpr int kImageBits = 6;
@@ -52,110 +48,16 @@ __device__ __forceinline__ int code_mol(int code) { return code >> kImageBits; }
 // what an edge adds to a packed translation
 __device__ __forceinline__ int code_step(int code) { return ((((code >> 4) & 3) - 1) << 16) + ((((code >> 2) & 3) - 1) << 8) + ((code & 3) - 1); }
 
-// s_a = (H^-1 r)_a reduced to [0, 1); I = H^-1, row-major
-__device__ __forceinline__ double frac_coord(const double* __restrict__ I, int a, double x, double y, double z)
-{
-    double s = __builtin_fma(I[3 * a], x, __builtin_fma(I[3 * a + 1], y, I[3 * a + 2] * z));
-    s = s - __builtin_floor(s);
-    return s >= 1.0 ? 0.0 : s;                 // (-1e-17 - floor = 1.0 after rounding)
-}
-
-// the cell of s along an axis of g cells, inside the table whatever s is
-__device__ __forceinline__ int cell_of(double s, int g)
-{
-    const int c = (int)(s * (double)g);
-    return c < 0 ? 0 : c >= g ? g - 1 : c;
-}
-
-// |H a|^2 (c = the cell's 9 doubles: c[3 k + a] = component a of h_(k+1))
+// |H a|^2: bond_vector without its components
 __device__ __forceinline__ double bond_r2(const double* __restrict__ c, double a0, double a1, double a2)
 {
-    const double dx = __builtin_fma(c[0], a0, __builtin_fma(c[3], a1, c[6] * a2));
-    const double dy = __builtin_fma(c[1], a0, __builtin_fma(c[4], a1, c[7] * a2));
-    const double dz = __builtin_fma(c[2], a0, __builtin_fma(c[5], a1, c[8] * a2));
-    return __builtin_fma(dx, dx, __builtin_fma(dy, dy, dz * dz));
-}
-
-// Offset o in {-1, 0, 1} from cell c of g: the cell it lands in and the image shift that goes with it.
-__device__ __forceinline__ void wrap_cell(int c, int o, int g, int& cw, int& shift)
-{
-    cw = c + o; shift = 0;
-    if (cw < 0) { cw += g; shift = -1; }
-    if (cw >= g) { cw -= g; shift = 1; }
-}
-
-// ---- general geometry: the counting sort ---------------------------------------------------------------------------------
-// par[box][18]: the cell (9) and its inverse (9).  grid[box][4]: g_1, g_2, g_3, cells.  Per box in scratch: su [n][3] fractional
-// positions by index, cid [n], tmp [n] (members of the cells in arrival order), cnt / start [cap + 1]; then in cell order:
-// idx [n] the molecule, ss [n][3].
-
-// One lane per molecule: s, its cell, the cell's count.
-__global__ __launch_bounds__(kThreads) void k_ring_bin(int n, int cap, const double* __restrict__ par, const int* __restrict__ grid,
-                                                       const double* __restrict__ pos, double* __restrict__ su, int* __restrict__ cid,
-                                                       int* __restrict__ cnt)
-{
-    const int b = blockIdx.y, i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n) return;
-    const double* I = par + 18 * (size_t)b + 9;
-    const int* g = grid + 4 * (size_t)b;
-    const size_t m = (size_t)b * n + i;
-    const double x = pos[3 * m], y = pos[3 * m + 1], z = pos[3 * m + 2];
-    const double s0 = frac_coord(I, 0, x, y, z), s1 = frac_coord(I, 1, x, y, z), s2 = frac_coord(I, 2, x, y, z);
-    su[3 * m] = s0; su[3 * m + 1] = s1; su[3 * m + 2] = s2;
-    const int c = (cell_of(s2, g[2]) * g[1] + cell_of(s1, g[1])) * g[0] + cell_of(s0, g[0]);
-    cid[m] = c;
-    atomicAdd(cnt + (size_t)b * (cap + 1) + c, 1);
-}
-
-// One workgroup per box: start[c] = the members of the cells before c, start[cells] = n.
-__global__ __launch_bounds__(kThreads) void k_ring_scan(int cap, const int* __restrict__ grid, const int* __restrict__ cnt, int* __restrict__ start)
-{
-    __shared__ int part[kThreads];
-    const int b = blockIdx.x, tid = threadIdx.x, cells = grid[4 * (size_t)b + 3];
-    const int* cn = cnt + (size_t)b * (cap + 1);
-    int* st = start + (size_t)b * (cap + 1);
-    const int per = (cells + kThreads - 1) / kThreads, c0 = min(tid * per, cells), c1 = min(c0 + per, cells);
-    int sum = 0;
-    for (int c = c0; c < c1; ++c) sum += cn[c];
-    part[tid] = sum;
-    __syncthreads();
-    int before = 0;
-    for (int t = 0; t < tid; ++t) before += part[t];
-    for (int c = c0; c < c1; ++c) { st[c] = before; before += cn[c]; }
-    if (tid == kThreads - 1) st[cells] = before;
-}
-
-// One lane per molecule: a place among its cell's members, in arrival order (k_ring_rank puts them in index order).
-__global__ __launch_bounds__(kThreads) void k_ring_place(int n, int cap, const int* __restrict__ cid, const int* __restrict__ start,
-                                                         int* __restrict__ cnt, int* __restrict__ tmp)
-{
-    const int b = blockIdx.y, i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n) return;
-    const size_t m = (size_t)b * n + i, t = (size_t)b * (cap + 1);
-    const int c = cid[m];
-    const int slot = start[t + c] + atomicSub(cnt + t + c, 1) - 1;
-    tmp[(size_t)b * n + slot] = i;
-}
-
-// One lane per member: its rank by molecule index among the members of its cell is its place in the sorted order.
-__global__ __launch_bounds__(kThreads) void k_ring_rank(int n, int cap, const int* __restrict__ cid, const int* __restrict__ start,
-                                                        const int* __restrict__ tmp, const double* __restrict__ su, int* __restrict__ idx,
-                                                        double* __restrict__ ss)
-{
-    const int b = blockIdx.y, p = blockIdx.x * kThreads + threadIdx.x;
-    if (p >= n) return;
-    const size_t o = (size_t)b * n, t = (size_t)b * (cap + 1);
-    const int i = tmp[o + p], c = cid[o + i];
-    const int q0 = start[t + c], q1 = start[t + c + 1];
-    int rank = 0;
-    for (int q = q0; q < q1; ++q) rank += tmp[o + q] < i ? 1 : 0;
-    const size_t d = o + q0 + rank;
-    idx[d] = i;
-    ss[3 * d] = su[3 * (o + i)]; ss[3 * d + 1] = su[3 * (o + i) + 1]; ss[3 * d + 2] = su[3 * (o + i) + 2];
+    double dx, dy, dz;
+    return bond_vector(c, a0, a1, a2, dx, dy, dz);
 }
 
 // ---- the adjacency pass --------------------------------------------------------------------------------------------------
-// Per box in scratch: ncount [n] the entries of every molecule, raw [n][8] its first 8 codes in the order of the walk.
+// Per box in scratch: ncount [n] the entries of every molecule, raw [n][8] its first 8 codes in the order of the walk.  Both
+// kernels write walk_cells' and walk_small's loops (mw_lib_cells.h) out: on the shared templates they took more registers.
 
 // General geometry, one lane per molecule in sorted order: the walk of the 27 cells, every offset with its own image shift.
 __global__ __launch_bounds__(kThreads) void k_ring_adj(int n, int cap, double rc2, const double* __restrict__ par, const int* __restrict__ grid,
@@ -203,7 +105,7 @@ __global__ __launch_bounds__(kThreads) void k_ring_adj(int n, int cap, double rc
 }
 
 // Small geometry, one wavefront per box, lane i = molecule i: j in index order and for each j the eight combinations of ds_k
-// and ds_k -/+ 1, the only two images per axis that can come within r_cut <= w_k.
+// and ds_k -/+ 1, the only two images per axis that can come within r_cut <= w_k -- walk_small's order and arithmetic.
 __global__ __launch_bounds__(64) void k_ring_small(int n, double rc2, const double* __restrict__ par, const double* __restrict__ pos,
                                                    int* __restrict__ ncount, int* __restrict__ raw, int* __restrict__ counts)
 {
@@ -485,31 +387,16 @@ struct State : Runtime<4> {
     float ms[3] = {0.0f, 0.0f, 0.0f};
 } g;
 
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-// The scratch of one box, piece by piece (byte offsets inside a chunk are these times boxes per chunk).  The small geometry
-// has the last four only.
-struct Layout {
-    int cap;                                                // cells a box may have
-    size_t su, cid, tmp, cnt, start, idx, ss, ncount, raw, row, lanes, per_box;
+// The scratch of one box: the sort's pieces (the small geometry has none of them), then the adjacency and the walk's.
+struct Layout : SortLayout {
+    size_t ncount, raw, row, lanes, per_box;
 };
 
 Layout make_layout(int n, bool small)
 {
     Layout l;
-    l.cap = 2 * n > 64 ? 2 * n : 64;
-    const size_t tab = align16(4 * ((size_t)l.cap + 1));
     size_t o = 0;
-    l.su = l.cid = l.tmp = l.cnt = l.start = l.idx = l.ss = 0;
-    if (!small) {
-        l.su = o;    o += align16(24 * (size_t)n);
-        l.cid = o;   o += align16(4 * (size_t)n);
-        l.tmp = o;   o += align16(4 * (size_t)n);
-        l.cnt = o;   o += tab;
-        l.start = o; o += tab;
-        l.idx = o;   o += align16(4 * (size_t)n);
-        l.ss = o;    o += align16(24 * (size_t)n);
-    }
+    if (!small) lay_sort(l, n, o);
     l.ncount = o; o += align16(4 * (size_t)n);
     l.raw = o;    o += 4 * (size_t)kDeg * n;
     l.row = o;    o += 4 * (size_t)kDeg * n;
@@ -518,10 +405,8 @@ Layout make_layout(int n, bool small)
     return l;
 }
 
-struct Plan {
-    int small, bpc, chunks, lds, boxes_per_wg;
+struct Plan : PlanBase {
     Layout lay;
-    size_t per_box;
 };
 
 constexpr int kWalkLds = 2 * 4 * kMaxRing * kWalkThreads + 4 * (2 * kSizes + 2);
@@ -543,38 +428,6 @@ int make_plan(const char* who, int n, int nboxes, size_t budget, Plan& p)
     return 0;
 }
 
-void plan_fields(const Plan& p, const int grid[3], int* f)
-{
-    f[0] = p.bpc; f[1] = p.chunks; f[2] = p.small; f[3] = grid[0]; f[4] = grid[1]; f[5] = grid[2];
-    f[6] = p.lds; f[7] = (int)p.per_box; f[8] = p.boxes_per_wg;
-}
-
-// w_k = |det| / |h_l x h_m|
-void cell_widths(const double* c, double det, double w[3])
-{
-    for (int k = 0; k < 3; ++k) {
-        const double* a = c + 3 * ((k + 1) % 3);
-        const double* b = c + 3 * ((k + 2) % 3);
-        const double x = a[1] * b[2] - a[2] * b[1], y = a[2] * b[0] - a[0] * b[2], z = a[0] * b[1] - a[1] * b[0];
-        w[k] = std::fabs(det) / std::sqrt(x * x + y * y + z * z);
-    }
-}
-
-// g_k = max(1, floor(w_k / (r_cut (1 + 1e-9)))), each at most kMaxGrid, the largest lowered until the product fits `cap` cells
-void cell_grid(const double w[3], double rc, int cap, int g[3])
-{
-    for (int k = 0; k < 3; ++k) {
-        const double f = std::floor(w[k] / (rc * kGuard));
-        g[k] = f >= (double)kMaxGrid ? kMaxGrid : f >= 1.0 ? (int)f : 1;
-    }
-    while ((long long)g[0] * g[1] * g[2] > cap) {
-        int k = 0;
-        if (g[1] > g[k]) k = 1;
-        if (g[2] > g[k]) k = 2;
-        --g[k];
-    }
-}
-
 int check_scalars(const char* who, int nboxes, int n, double rc)
 {
     if (nboxes < 1 || nboxes > kMaxBoxes) return fail("%s: nboxes = %d outside 1..%d", who, nboxes, kMaxBoxes);
@@ -583,30 +436,7 @@ int check_scalars(const char* who, int nboxes, int n, double rc)
     return 0;
 }
 
-// Every box's cell: invertible, and no narrower than r_cut (1 + 1e-9).  Fills par [nboxes][18] and grid [nboxes][4].
-int check_cells(const char* who, int nboxes, int n, const double* cells, double rc, std::vector<double>& par, std::vector<int>& grid)
-{
-    par.resize(18 * (size_t)nboxes);
-    grid.resize(4 * (size_t)nboxes);
-    const int cap = make_layout(n, false).cap;
-    for (int b = 0; b < nboxes; ++b) {
-        const double* c = cells + 9 * (size_t)b;
-        double* P = par.data() + 18 * (size_t)b;
-        double det, w[3];
-        if (!invert_cell(c, P + 9, &det))
-            return fail("%s: cells: the determinant of box %d is %g (zero or not finite)", who, b, det);
-        memcpy(P, c, 9 * sizeof(double));
-        cell_widths(c, det, w);
-        const double wmin = std::fmin(w[0], std::fmin(w[1], w[2]));
-        if (!(rc * kGuard <= wmin))
-            return fail("%s: r_cut = %.17g bohr is beyond the narrowest width %.17g bohr of box %d (r_cut (1 + 1e-9) <= every cell "
-                        "width is required)", who, rc, wmin, b);
-        int* G = grid.data() + 4 * (size_t)b;
-        cell_grid(w, rc, cap, G);
-        G[3] = G[0] * G[1] * G[2];
-    }
-    return 0;
-}
+const char kRadius[] = "r_cut";               // the radius the cells are checked against, in the messages
 
 // what both compute entries can check on the host before they look at the library's state
 int check_host_side(const char* who, int nboxes, int n, const double* cells, const double* pos, double rc, int list_cap)
@@ -619,8 +449,6 @@ int check_host_side(const char* who, int nboxes, int n, const double* cells, con
 }
 
 int check_live(const char* who) { return check_live(who, "mw_rings_init", g); }
-
-dim3 per_molecule(int n, int nb, int threads) { return dim3((unsigned)((n + threads - 1) / threads), (unsigned)nb); }
 
 // The work of both entries, arguments already checked.  par and grid are on the host; pos and the outputs are device pointers
 // when `dev`, host pointers otherwise.
@@ -678,32 +506,16 @@ int run(const char* who, int nboxes, int n, const std::vector<double>& par, cons
             hipLaunchKernelGGL(k_ring_small, dim3((unsigned)nb), dim3(64), 0, g.stream, n, rc2, d_par, d_pos, ncount, raw, d_counts);
             HIPOK(hipGetLastError());
         } else {
-            double* su = (double*)(base + l.su * B);
-            int* cid = (int*)(base + l.cid * B);
-            int* tmp = (int*)(base + l.tmp * B);
-            int* cnt = (int*)(base + l.cnt * B);
-            int* start = (int*)(base + l.start * B);
-            int* idx = (int*)(base + l.idx * B);
-            double* ss = (double*)(base + l.ss * B);
-            const dim3 grid_m = per_molecule(n, nb, kThreads);
-            HIPOK(hipMemsetAsync(cnt, 0, 4 * ((size_t)l.cap + 1) * nb, g.stream));
-            hipLaunchKernelGGL(k_ring_bin, grid_m, dim3(kThreads), 0, g.stream, n, l.cap, d_par, d_grid, d_pos, su, cid, cnt);
-            HIPOK(hipGetLastError());
-            hipLaunchKernelGGL(k_ring_scan, dim3((unsigned)nb), dim3(kThreads), 0, g.stream, l.cap, d_grid, (const int*)cnt, start);
-            HIPOK(hipGetLastError());
-            hipLaunchKernelGGL(k_ring_place, grid_m, dim3(kThreads), 0, g.stream, n, l.cap, (const int*)cid, (const int*)start, cnt, tmp);
-            HIPOK(hipGetLastError());
-            hipLaunchKernelGGL(k_ring_rank, grid_m, dim3(kThreads), 0, g.stream, n, l.cap, (const int*)cid, (const int*)start, (const int*)tmp,
-                               (const double*)su, idx, ss);
-            HIPOK(hipGetLastError());
+            Sorted s;
+            if (sort_into_cells(g.stream, n, nb, l, base, B, d_par, d_grid, d_pos, s)) return 1;
             HIPOK(hipEventRecord(g.ev[1], g.stream));
-            hipLaunchKernelGGL(k_ring_adj, grid_m, dim3(kThreads), 0, g.stream, n, l.cap, rc2, d_par, d_grid, (const int*)start, (const double*)ss,
-                               (const int*)idx, ncount, raw, d_counts);
+            hipLaunchKernelGGL(k_ring_adj, per_molecule(n, nb), dim3(kThreads), 0, g.stream, n, l.cap, rc2, d_par, d_grid, s.start, s.ss, s.idx,
+                               ncount, raw, d_counts);
             HIPOK(hipGetLastError());
         }
         if (walk) {
             if (d_sum) HIPOK(hipMemsetAsync(d_sum, 0, 8 * (size_t)kSums * nb, g.stream));
-            hipLaunchKernelGGL(k_ring_rows, per_molecule(n, nb, kThreads), dim3(kThreads), 0, g.stream, n, (const int*)ncount, (const int*)raw, row,
+            hipLaunchKernelGGL(k_ring_rows, per_molecule(n, nb), dim3(kThreads), 0, g.stream, n, (const int*)ncount, (const int*)raw, row,
                                d_sum);
             HIPOK(hipGetLastError());
         }
@@ -774,7 +586,7 @@ int mw_rings_compute(int nboxes, int nwater, const double* cells, const double* 
     std::vector<double> par;
     std::vector<int> grid;
     if (check_host_side(who, nboxes, nwater, cells, pos, r_cut, list_cap)) return 1;
-    if (check_cells(who, nboxes, nwater, cells, r_cut, par, grid)) return 1;
+    if (check_cells(who, kRadius, nboxes, nwater, cells, r_cut, par, grid)) return 1;
     if (check_live(who)) return 1;
     return run(who, nboxes, nwater, par, grid, pos, r_cut, list_cap, false, hist, closed, member, counts, summary, list);
 }
@@ -789,22 +601,16 @@ int mw_rings_compute_device(int nboxes, int nwater, const double* cells, const d
     if (check_live(who)) return 1;
     DeviceScope scope;
     HIPOK(scope.enter(g.device));
-    HIPOK(hipDeviceSynchronize());                            // whoever made the inputs (another stream, PyTorch's) is done
-    std::vector<double> h_cells(9 * (size_t)nboxes);
-    HIPOK(hipMemcpy(h_cells.data(), cells, h_cells.size() * sizeof(double), hipMemcpyDeviceToHost));
-    if (check_cells(who, nboxes, nwater, h_cells.data(), r_cut, par, grid)) return 1;
+    if (fetch_cells(who, kRadius, nboxes, nwater, cells, r_cut, par, grid)) return 1;
     return run(who, nboxes, nwater, par, grid, pos, r_cut, list_cap, true, hist, closed, member, counts, summary, list);
 }
 
 int mw_rings_plan(int nwater, const double* cell, double r_cut, int nboxes, int* out, int nout)
 {
     const char* who = "mw_rings_plan";
-    std::vector<double> par;
     std::vector<int> grid;
     if (check_scalars(who, nboxes, nwater, r_cut)) return 1;
-    if (!cell) return fail("%s: cell is NULL", who);
-    if (!out || nout < 1) return fail("%s: out is NULL or nout < 1", who);
-    if (check_cells(who, 1, nwater, cell, r_cut, par, grid)) return 1;
+    if (plan_grid(who, kRadius, nwater, cell, r_cut, out, nout, grid)) return 1;
     Plan p;
     if (make_plan(who, nwater, nboxes, g.live ? g.budget : kDefaultBudget, p)) return 1;
     int f[MW_RINGS_PLAN_FIELDS];
@@ -813,14 +619,7 @@ int mw_rings_plan(int nwater, const double* cell, double r_cut, int nboxes, int*
     return 0;
 }
 
-int mw_rings_last(int* out, int nout)
-{
-    if (check_live("mw_rings_last")) return 1;
-    if (!out || nout < 1) return fail("mw_rings_last: out is NULL or nout < 1");
-    if (!g.have_last) return fail("mw_rings_last: no call has launched yet");
-    copy_fields(g.last, MW_RINGS_PLAN_FIELDS, out, nout);
-    return 0;
-}
+int mw_rings_last(int* out, int nout) { return last_fields("mw_rings_last", "mw_rings_init", g, g.last, MW_RINGS_PLAN_FIELDS, out, nout); }
 
 int mw_rings_elapsed_ms(float* binning, float* adjacency, float* walk)
 {

@@ -1,12 +1,12 @@
 // libmw_tet.so -- the nearest-neighbour order parameters of include/mw_tet.h: the tetrahedral order q, its translational
 // companion s_k, the fifth-neighbour distance d5 and the local structure index of every molecule, the four nearest
 // neighbours and the box means, for many boxes.  General geometry (nwater > 64): a counting sort into a fractional cell grid
-// (k_tet_bin, k_tet_scan, k_tet_place, k_tet_rank), then k_tet_select, one lane per molecule in sorted order, walks the 27
+// (the sort of mw_lib_cells.h), then k_tet_select, one lane per molecule in sorted order, walks the 27
 // neighbouring cells and keeps the 16 nearest entries sorted in registers, and k_tet_summary adds the box up.  Small geometry
 // (nwater <= 64): k_tet_small, one wavefront per box with the box in LDS.  Every bit of a box's results depends on the box and
 // the two radii alone (mw_tet.h): the arithmetic below is spelled out in fma / mul / add with contraction off, and the order
-// of every sum and of every ranking is fixed.  (The binning kernels and the grid rules are those of mw_boo.hip, written out
-// again here: the two libraries share host code only.)
+// of every sum and of every ranking is fixed.  The grid rules, the sort and the two walks are mw_lib_cells.h's, shared with
+// libmw_boo.so and the other libraries that sort into a cell grid.
 #include "../../include/mw_tet.h"
 
 #include "mw_common.hip.h"
@@ -17,59 +17,22 @@
 #pragma clang fp contract(off)
 
 #include "mw_lib_host.h"                       // after the pragma: its host arithmetic is uncontracted too
+#include "mw_lib_cells.h"
 
 namespace mwtet {
 
-constexpr int kThreads = 256;
-constexpr int kSmallN = 64;
+using namespace mwcells;
+
 constexpr int kSmallBoxesPerWg = kThreads / 64;   // one wavefront per box
 constexpr int kKeep = MW_TET_KEEP;
 constexpr int kOrd = 4;                           // doubles per molecule in scratch: q, s_k, d5, lsi
 constexpr int kSums = 8;                          // box sums: the four values over the molecules where defined, and how many
-constexpr int kMaxGrid = 1024;
-constexpr int kMaxWater = 1 << 22;
-constexpr int kMaxBoxes = 1 << 24;
-constexpr int kMaxChunkBoxes = 65535;             // grid y
-constexpr int kSmallChunkBoxes = 1 << 20;
-constexpr double kGuard = 1.0 + 1e-9;
 constexpr int kSmallLds = kSmallBoxesPerWg * 3 * 64 * 8;
 constexpr int kPlaceBits = 22;                    // an entry: the place (or index) of j in the low bits, its image above
 constexpr int kPlaceMask = (1 << kPlaceBits) - 1;
 static_assert(kMaxWater <= (1 << kPlaceBits), "an entry holds a molecule in kPlaceBits bits");
 
 __device__ __forceinline__ double undefined() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-// s_a = (H^-1 r)_a reduced to [0, 1); I = H^-1, row-major
-__device__ __forceinline__ double frac_coord(const double* __restrict__ I, int a, double x, double y, double z)
-{
-    double s = __builtin_fma(I[3 * a], x, __builtin_fma(I[3 * a + 1], y, I[3 * a + 2] * z));
-    s = s - __builtin_floor(s);
-    return s >= 1.0 ? 0.0 : s;                 // (-1e-17 - floor = 1.0 after rounding)
-}
-
-// the cell of s along an axis of g cells, inside the table whatever s is
-__device__ __forceinline__ int cell_of(double s, int g)
-{
-    const int c = (int)(s * (double)g);
-    return c < 0 ? 0 : c >= g ? g - 1 : c;
-}
-
-// d = H ds (c = the cell's 9 doubles: c[3 k + a] = component a of h_(k+1)); returns |d|^2
-__device__ __forceinline__ double bond_vector(const double* __restrict__ c, double a0, double a1, double a2, double& dx, double& dy, double& dz)
-{
-    dx = __builtin_fma(c[0], a0, __builtin_fma(c[3], a1, c[6] * a2));
-    dy = __builtin_fma(c[1], a0, __builtin_fma(c[4], a1, c[7] * a2));
-    dz = __builtin_fma(c[2], a0, __builtin_fma(c[5], a1, c[8] * a2));
-    return __builtin_fma(dx, dx, __builtin_fma(dy, dy, dz * dz));
-}
-
-// Offset o in {-1, 0, 1} from cell c of g: the cell it lands in and the image shift that goes with it.
-__device__ __forceinline__ void wrap_cell(int c, int o, int g, int& cw, int& shift)
-{
-    cw = c + o; shift = 0;
-    if (cw < 0) { cw += g; shift = -1; }
-    if (cw >= g) { cw -= g; shift = 1; }
-}
 
 // ---- the 16 nearest, sorted in registers ---------------------------------------------------------------------------------
 // k[a] / e[a]: r^2 and the entry of rank a + 1, +inf / -1 where there is none yet.  Every index below is a compile-time
@@ -165,74 +128,7 @@ __device__ __forceinline__ void write_summary(const double* t, double* out)
 }
 
 // ---- general geometry ----------------------------------------------------------------------------------------------------
-// par[box][18]: the cell (9) and its inverse (9).  grid[box][4]: g_1, g_2, g_3, cells.  Per box in scratch: su [n][3] fractional
-// positions by index, cid [n], tmp [n] (members of the cells in arrival order), cnt / start [cap + 1]; then in cell order:
-// idx [n] the molecule, ss [n][3], ord [n][kOrd].
-
-// One lane per molecule: s, its cell, the cell's count.
-__global__ __launch_bounds__(kThreads) void k_tet_bin(int n, int cap, const double* __restrict__ par, const int* __restrict__ grid,
-                                                      const double* __restrict__ pos, double* __restrict__ su, int* __restrict__ cid,
-                                                      int* __restrict__ cnt)
-{
-    const int b = blockIdx.y, i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n) return;
-    const double* I = par + 18 * (size_t)b + 9;
-    const int* g = grid + 4 * (size_t)b;
-    const size_t m = (size_t)b * n + i;
-    const double x = pos[3 * m], y = pos[3 * m + 1], z = pos[3 * m + 2];
-    const double s0 = frac_coord(I, 0, x, y, z), s1 = frac_coord(I, 1, x, y, z), s2 = frac_coord(I, 2, x, y, z);
-    su[3 * m] = s0; su[3 * m + 1] = s1; su[3 * m + 2] = s2;
-    const int c = (cell_of(s2, g[2]) * g[1] + cell_of(s1, g[1])) * g[0] + cell_of(s0, g[0]);
-    cid[m] = c;
-    atomicAdd(cnt + (size_t)b * (cap + 1) + c, 1);
-}
-
-// One workgroup per box: start[c] = the members of the cells before c, start[cells] = n.
-__global__ __launch_bounds__(kThreads) void k_tet_scan(int cap, const int* __restrict__ grid, const int* __restrict__ cnt, int* __restrict__ start)
-{
-    __shared__ int part[kThreads];
-    const int b = blockIdx.x, tid = threadIdx.x, cells = grid[4 * (size_t)b + 3];
-    const int* cn = cnt + (size_t)b * (cap + 1);
-    int* st = start + (size_t)b * (cap + 1);
-    const int per = (cells + kThreads - 1) / kThreads, c0 = min(tid * per, cells), c1 = min(c0 + per, cells);
-    int sum = 0;
-    for (int c = c0; c < c1; ++c) sum += cn[c];
-    part[tid] = sum;
-    __syncthreads();
-    int before = 0;
-    for (int t = 0; t < tid; ++t) before += part[t];
-    for (int c = c0; c < c1; ++c) { st[c] = before; before += cn[c]; }
-    if (tid == kThreads - 1) st[cells] = before;
-}
-
-// One lane per molecule: a place among its cell's members, in arrival order (k_tet_rank puts them in index order).
-__global__ __launch_bounds__(kThreads) void k_tet_place(int n, int cap, const int* __restrict__ cid, const int* __restrict__ start,
-                                                        int* __restrict__ cnt, int* __restrict__ tmp)
-{
-    const int b = blockIdx.y, i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n) return;
-    const size_t m = (size_t)b * n + i, t = (size_t)b * (cap + 1);
-    const int c = cid[m];
-    const int slot = start[t + c] + atomicSub(cnt + t + c, 1) - 1;
-    tmp[(size_t)b * n + slot] = i;
-}
-
-// One lane per member: its rank by molecule index among the members of its cell is its place in the sorted order.
-__global__ __launch_bounds__(kThreads) void k_tet_rank(int n, int cap, const int* __restrict__ cid, const int* __restrict__ start,
-                                                       const int* __restrict__ tmp, const double* __restrict__ su, int* __restrict__ idx,
-                                                       double* __restrict__ ss)
-{
-    const int b = blockIdx.y, p = blockIdx.x * kThreads + threadIdx.x;
-    if (p >= n) return;
-    const size_t o = (size_t)b * n, t = (size_t)b * (cap + 1);
-    const int i = tmp[o + p], c = cid[o + i];
-    const int q0 = start[t + c], q1 = start[t + c + 1];
-    int rank = 0;
-    for (int q = q0; q < q1; ++q) rank += tmp[o + q] < i ? 1 : 0;
-    const size_t d = o + q0 + rank;
-    idx[d] = i;
-    ss[3 * d] = su[3 * (o + i)]; ss[3 * d + 1] = su[3 * (o + i) + 1]; ss[3 * d + 2] = su[3 * (o + i) + 2];
-}
+// Per box in scratch after the sort's pieces (mw_lib_cells.h): ord [n][kOrd] in cell order.
 
 // The selection pass, one lane per molecule in sorted order: the walk of the 27 cells in the contract's order, every entry
 // within r_search offered to the lane's Nearest; then the values of the molecule.  An entry is the sorted place of j with the
@@ -245,36 +141,14 @@ __global__ __launch_bounds__(kThreads) void k_tet_select(int n, int cap, double 
     const int b = blockIdx.y, p = blockIdx.x * kThreads + threadIdx.x;
     if (p >= n) return;
     const double* H = par + 18 * (size_t)b;
-    const int* g = grid + 4 * (size_t)b;
-    const int* st = start + (size_t)b * (cap + 1);
     const size_t o = (size_t)b * n;
     const double* S = ss + 3 * o;
     const double s0 = S[3 * (size_t)p], s1 = S[3 * (size_t)p + 1], s2 = S[3 * (size_t)p + 2];
-    const int g0 = g[0], g1 = g[1], g2 = g[2];
-    const int c0 = cell_of(s0, g0), c1 = cell_of(s1, g1), c2 = cell_of(s2, g2);
     Nearest t;
-    for (int oz = -1; oz <= 1; ++oz) {
-        int wz, hz;
-        wrap_cell(c2, oz, g2, wz, hz);
-        for (int oy = -1; oy <= 1; ++oy) {
-            int wy, hy;
-            wrap_cell(c1, oy, g1, wy, hy);
-            for (int ox = -1; ox <= 1; ++ox) {
-                int wx, hx;
-                wrap_cell(c0, ox, g0, wx, hx);
-                const int c = (wz * g1 + wy) * g0 + wx;
-                const int image = (((hz + 1) * 3 + (hy + 1)) * 3 + (hx + 1)) << kPlaceBits;
-                const double fx = (double)hx, fy = (double)hy, fz = (double)hz;
-                const int q1 = st[c + 1];
-                for (int q = st[c]; q < q1; ++q) {
-                    const double a0 = (S[3 * (size_t)q] - s0) + fx, a1 = (S[3 * (size_t)q + 1] - s1) + fy, a2 = (S[3 * (size_t)q + 2] - s2) + fz;
-                    double dx, dy, dz;
-                    const double r2 = bond_vector(H, a0, a1, a2, dx, dy, dz);
-                    if (r2 < rs2 && r2 > 0.0) t.add(r2, rl2, image | q);
-                }
-            }
-        }
-    }
+    walk_cells(s0, s1, s2, rs2, H, grid + 4 * (size_t)b, start + (size_t)b * (cap + 1), S,
+               [&](int q, int hx, int hy, int hz, double r2, double, double, double) {
+                   t.add(r2, rl2, ((((hz + 1) * 3 + (hy + 1)) * 3 + (hx + 1)) << kPlaceBits) | q);
+               });
     double d[4][3];
     int who[4];
 #pragma unroll
@@ -336,9 +210,7 @@ __global__ __launch_bounds__(kThreads) void k_tet_summary(int n, const double* _
 }
 
 // ---- small geometry: one wavefront per box, lane i = molecule i, the box's fractional positions in LDS ----------------------
-// The entries of i: j in index order, and for each j the eight combinations of ds_k and ds_k -/+ 1 (the only two images per
-// axis that can come within r_search <= w_k), combination bit k choosing the second along axis k.  An entry is j with the
-// combination above it.
+// The entries of i in walk_small's order; an entry is j with the image combination above it.
 __global__ __launch_bounds__(kThreads) void k_tet_small(int nb, int n, double rs2, double rl2, const double* __restrict__ par,
                                                         const double* __restrict__ pos, double* __restrict__ order, int* __restrict__ near_,
                                                         int* __restrict__ counts, double* __restrict__ summary)
@@ -358,16 +230,7 @@ __global__ __launch_bounds__(kThreads) void k_tet_small(int nb, int n, double rs
     mw::wave_fence();
 
     Nearest t;
-    for (int j = 0; j < n; ++j) {
-        const double e0 = S[j] - s0, e1 = S[64 + j] - s1, e2 = S[128 + j] - s2;
-        const double f0 = e0 > 0.0 ? e0 - 1.0 : e0 + 1.0, f1 = e1 > 0.0 ? e1 - 1.0 : e1 + 1.0, f2 = e2 > 0.0 ? e2 - 1.0 : e2 + 1.0;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            double dx, dy, dz;
-            const double r2 = bond_vector(H, (c & 1) ? f0 : e0, (c & 2) ? f1 : e1, (c & 4) ? f2 : e2, dx, dy, dz);
-            if (active && r2 < rs2 && r2 > 0.0) t.add(r2, rl2, (c << kPlaceBits) | j);
-        }
-    }
+    walk_small(n, active, rs2, H, S, s0, s1, s2, [&](int j, int c, double r2, double, double, double) { t.add(r2, rl2, (c << kPlaceBits) | j); });
     double d[4][3];
     int who[4];
 #pragma unroll
@@ -413,36 +276,23 @@ struct State : Runtime<4> {
     float ms[3] = {0.0f, 0.0f, 0.0f};
 } g;
 
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-// The scratch of one box of the general geometry, piece by piece (byte offsets inside a chunk are these times boxes per chunk).
-struct Layout {
-    int cap;                                                // cells a box may have
-    size_t su, cid, tmp, cnt, start, idx, ss, ord, per_box;
+// The scratch of one box of the general geometry: the sort's pieces, then ord.
+struct Layout : SortLayout {
+    size_t ord, per_box;
 };
 
 Layout make_layout(int n)
 {
     Layout l;
-    l.cap = 2 * n > 64 ? 2 * n : 64;
-    const size_t tab = align16(4 * ((size_t)l.cap + 1));
     size_t o = 0;
-    l.su = o;    o += align16(24 * (size_t)n);
-    l.cid = o;   o += align16(4 * (size_t)n);
-    l.tmp = o;   o += align16(4 * (size_t)n);
-    l.cnt = o;   o += tab;
-    l.start = o; o += tab;
-    l.idx = o;   o += align16(4 * (size_t)n);
-    l.ss = o;    o += align16(24 * (size_t)n);
+    lay_sort(l, n, o);
     l.ord = o;   o += align16(8 * (size_t)kOrd * n);
     l.per_box = o;
     return l;
 }
 
-struct Plan {
-    int small, bpc, chunks, lds, boxes_per_wg;
+struct Plan : PlanBase {
     Layout lay;
-    size_t per_box;
 };
 
 int make_plan(const char* who, int n, int nboxes, size_t budget, Plan& p)
@@ -465,38 +315,6 @@ int make_plan(const char* who, int n, int nboxes, size_t budget, Plan& p)
     return 0;
 }
 
-void plan_fields(const Plan& p, const int grid[3], int* f)
-{
-    f[0] = p.bpc; f[1] = p.chunks; f[2] = p.small; f[3] = grid[0]; f[4] = grid[1]; f[5] = grid[2];
-    f[6] = p.lds; f[7] = (int)p.per_box; f[8] = p.boxes_per_wg;
-}
-
-// w_k = |det| / |h_l x h_m|
-void cell_widths(const double* c, double det, double w[3])
-{
-    for (int k = 0; k < 3; ++k) {
-        const double* a = c + 3 * ((k + 1) % 3);
-        const double* b = c + 3 * ((k + 2) % 3);
-        const double x = a[1] * b[2] - a[2] * b[1], y = a[2] * b[0] - a[0] * b[2], z = a[0] * b[1] - a[1] * b[0];
-        w[k] = std::fabs(det) / std::sqrt(x * x + y * y + z * z);
-    }
-}
-
-// g_k = max(1, floor(w_k / (r_search (1 + 1e-9)))), each at most kMaxGrid, the largest lowered until the product fits `cap` cells
-void cell_grid(const double w[3], double rs, int cap, int g[3])
-{
-    for (int k = 0; k < 3; ++k) {
-        const double f = std::floor(w[k] / (rs * kGuard));
-        g[k] = f >= (double)kMaxGrid ? kMaxGrid : f >= 1.0 ? (int)f : 1;
-    }
-    while ((long long)g[0] * g[1] * g[2] > cap) {
-        int k = 0;
-        if (g[1] > g[k]) k = 1;
-        if (g[2] > g[k]) k = 2;
-        --g[k];
-    }
-}
-
 int check_scalars(const char* who, int nboxes, int n, double rs, double rl)
 {
     if (nboxes < 1 || nboxes > kMaxBoxes) return fail("%s: nboxes = %d outside 1..%d", who, nboxes, kMaxBoxes);
@@ -507,34 +325,9 @@ int check_scalars(const char* who, int nboxes, int n, double rs, double rl)
     return 0;
 }
 
-// Every box's cell: invertible, and no narrower than r_search (1 + 1e-9).  Fills par [nboxes][18] and grid [nboxes][4].
-int check_cells(const char* who, int nboxes, int n, const double* cells, double rs, std::vector<double>& par, std::vector<int>& grid)
-{
-    par.resize(18 * (size_t)nboxes);
-    grid.resize(4 * (size_t)nboxes);
-    const int cap = make_layout(n).cap;
-    for (int b = 0; b < nboxes; ++b) {
-        const double* c = cells + 9 * (size_t)b;
-        double* P = par.data() + 18 * (size_t)b;
-        double det, w[3];
-        if (!invert_cell(c, P + 9, &det))
-            return fail("%s: cells: the determinant of box %d is %g (zero or not finite)", who, b, det);
-        memcpy(P, c, 9 * sizeof(double));
-        cell_widths(c, det, w);
-        const double wmin = std::fmin(w[0], std::fmin(w[1], w[2]));
-        if (!(rs * kGuard <= wmin))
-            return fail("%s: r_search = %.17g bohr is beyond the narrowest width %.17g bohr of box %d (r_search (1 + 1e-9) <= every cell "
-                        "width is required)", who, rs, wmin, b);
-        int* G = grid.data() + 4 * (size_t)b;
-        cell_grid(w, rs, cap, G);
-        G[3] = G[0] * G[1] * G[2];
-    }
-    return 0;
-}
+const char kRadius[] = "r_search";            // the radius the cells are checked against, in the messages
 
 int check_live(const char* who) { return check_live(who, "mw_tet_init", g); }
-
-dim3 per_molecule(int n, int nb) { return dim3((unsigned)((n + kThreads - 1) / kThreads), (unsigned)nb); }
 
 // The work of both entries, arguments already checked.  par and grid are on the host; pos and the outputs are device pointers
 // when `dev`, host pointers otherwise.
@@ -584,29 +377,14 @@ int run(const char* who, int nboxes, int n, const std::vector<double>& par, cons
             if (!d_sum) d_sum = (double*)g.summary.p;
             char* base = (char*)g.scratch.p;
             const size_t B = (size_t)p.bpc;
-            double* su = (double*)(base + l.su * B);
-            int* cid = (int*)(base + l.cid * B);
-            int* tmp = (int*)(base + l.tmp * B);
-            int* cnt = (int*)(base + l.cnt * B);
-            int* start = (int*)(base + l.start * B);
-            int* idx = (int*)(base + l.idx * B);
-            double* ss = (double*)(base + l.ss * B);
             double* ord = (double*)(base + l.ord * B);
             const dim3 grid_m = per_molecule(n, nb);
+            Sorted s;
             HIPOK(hipEventRecord(g.ev[0], g.stream));
-            HIPOK(hipMemsetAsync(cnt, 0, 4 * ((size_t)l.cap + 1) * nb, g.stream));
-            hipLaunchKernelGGL(k_tet_bin, grid_m, dim3(kThreads), 0, g.stream, n, l.cap, d_par, d_grid, d_pos, su, cid, cnt);
-            HIPOK(hipGetLastError());
-            hipLaunchKernelGGL(k_tet_scan, dim3((unsigned)nb), dim3(kThreads), 0, g.stream, l.cap, d_grid, (const int*)cnt, start);
-            HIPOK(hipGetLastError());
-            hipLaunchKernelGGL(k_tet_place, grid_m, dim3(kThreads), 0, g.stream, n, l.cap, (const int*)cid, (const int*)start, cnt, tmp);
-            HIPOK(hipGetLastError());
-            hipLaunchKernelGGL(k_tet_rank, grid_m, dim3(kThreads), 0, g.stream, n, l.cap, (const int*)cid, (const int*)start, (const int*)tmp,
-                               (const double*)su, idx, ss);
-            HIPOK(hipGetLastError());
+            if (sort_into_cells(g.stream, n, nb, l, base, B, d_par, d_grid, d_pos, s)) return 1;
             HIPOK(hipEventRecord(g.ev[1], g.stream));
-            hipLaunchKernelGGL(k_tet_select, grid_m, dim3(kThreads), 0, g.stream, n, l.cap, rs2, rl2, d_par, d_grid, (const int*)start,
-                               (const double*)ss, (const int*)idx, ord, d_order, d_near, d_counts);
+            hipLaunchKernelGGL(k_tet_select, grid_m, dim3(kThreads), 0, g.stream, n, l.cap, rs2, rl2, d_par, d_grid, s.start, s.ss, s.idx, ord,
+                               d_order, d_near, d_counts);
             HIPOK(hipGetLastError());
             HIPOK(hipEventRecord(g.ev[2], g.stream));
             hipLaunchKernelGGL(k_tet_summary, dim3((unsigned)nb), dim3(kThreads), 0, g.stream, n, (const double*)ord, d_sum);
@@ -663,7 +441,7 @@ int mw_tet_compute(int nboxes, int nwater, const double* cells, const double* po
     if (check_scalars(who, nboxes, nwater, r_search, r_lsi)) return 1;
     if (!cells) return fail("%s: cells is NULL", who);
     if (!pos) return fail("%s: pos is NULL", who);
-    if (check_cells(who, nboxes, nwater, cells, r_search, par, grid)) return 1;
+    if (check_cells(who, kRadius, nboxes, nwater, cells, r_search, par, grid)) return 1;
     if (check_live(who)) return 1;
     return run(who, nboxes, nwater, par, grid, pos, r_search, r_lsi, false, order, near_, counts, summary);
 }
@@ -680,22 +458,16 @@ int mw_tet_compute_device(int nboxes, int nwater, const double* cells, const dou
     if (check_live(who)) return 1;
     DeviceScope scope;
     HIPOK(scope.enter(g.device));
-    HIPOK(hipDeviceSynchronize());                            // whoever made the inputs (another stream, PyTorch's) is done
-    std::vector<double> h_cells(9 * (size_t)nboxes);
-    HIPOK(hipMemcpy(h_cells.data(), cells, h_cells.size() * sizeof(double), hipMemcpyDeviceToHost));
-    if (check_cells(who, nboxes, nwater, h_cells.data(), r_search, par, grid)) return 1;
+    if (fetch_cells(who, kRadius, nboxes, nwater, cells, r_search, par, grid)) return 1;
     return run(who, nboxes, nwater, par, grid, pos, r_search, r_lsi, true, order, near_, counts, summary);
 }
 
 int mw_tet_plan(int nwater, const double* cell, double r_search, int nboxes, int* out, int nout)
 {
     const char* who = "mw_tet_plan";
-    std::vector<double> par;
     std::vector<int> grid;
     if (check_scalars(who, nboxes, nwater, r_search, r_search)) return 1;
-    if (!cell) return fail("%s: cell is NULL", who);
-    if (!out || nout < 1) return fail("%s: out is NULL or nout < 1", who);
-    if (check_cells(who, 1, nwater, cell, r_search, par, grid)) return 1;
+    if (plan_grid(who, kRadius, nwater, cell, r_search, out, nout, grid)) return 1;
     Plan p;
     if (make_plan(who, nwater, nboxes, g.live ? g.budget : kDefaultBudget, p)) return 1;
     int f[MW_TET_PLAN_FIELDS];
@@ -704,14 +476,7 @@ int mw_tet_plan(int nwater, const double* cell, double r_search, int nboxes, int
     return 0;
 }
 
-int mw_tet_last(int* out, int nout)
-{
-    if (check_live("mw_tet_last")) return 1;
-    if (!out || nout < 1) return fail("mw_tet_last: out is NULL or nout < 1");
-    if (!g.have_last) return fail("mw_tet_last: no call has launched yet");
-    copy_fields(g.last, MW_TET_PLAN_FIELDS, out, nout);
-    return 0;
-}
+int mw_tet_last(int* out, int nout) { return last_fields("mw_tet_last", "mw_tet_init", g, g.last, MW_TET_PLAN_FIELDS, out, nout); }
 
 int mw_tet_elapsed_ms(float* binning, float* select, float* summary)
 {

@@ -13,7 +13,7 @@ import pytest
 from conftest import ROOT, load_golden
 
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-KERNELS = (b"k_boo_bin", b"k_boo_scan", b"k_boo_place", b"k_boo_rank", b"k_boo_pass1", b"k_boo_pass2", b"k_boo_summary", b"k_boo_small")
+KERNELS = (b"k_cells_bin", b"k_cells_scan", b"k_cells_place", b"k_cells_rank", b"k_boo_pass1", b"k_boo_pass2", b"k_boo_summary", b"k_boo_small")
 ANG_TO_BOHR = 1.0 / 0.5291772108
 
 
@@ -44,6 +44,8 @@ def test_build_boo_compiles_for_gfx950():
     assert not any(p in build.SK_DEPS for p in (build.BOO_SRC, header))
     shared = os.path.join(build.CSRC, "mw_lib_host.h")                          # the host layer both device libraries include
     assert shared in build.SK_DEPS and shared in build.BOO_DEPS and shared not in build.DEPS
+    cells = os.path.join(build.CSRC, "mw_lib_cells.h")                          # the cell grid, sort and walks; not a .hip.h, so not libmw_hip.so's
+    assert cells in build.BOO_DEPS and cells not in build.DEPS and cells not in build.SK_DEPS
     assert os.path.basename(build.BOO_SRC) == "mw_boo.hip" and not any("boo" in f for f in os.listdir(build.CSRC) if f.endswith(".hip.h"))
 
 

@@ -14,7 +14,7 @@ import pytest
 from conftest import ROOT, load_golden
 
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-KERNELS = (b"k_ring_bin", b"k_ring_scan", b"k_ring_place", b"k_ring_rank", b"k_ring_adj", b"k_ring_small", b"k_ring_rows", b"k_ring_walk",
+KERNELS = (b"k_cells_bin", b"k_cells_scan", b"k_cells_place", b"k_cells_rank", b"k_ring_adj", b"k_ring_small", b"k_ring_rows", b"k_ring_walk",
            b"k_ring_offsets")
 ANG_TO_BOHR = 1.0 / 0.5291772108
 
@@ -43,7 +43,9 @@ def test_build_rings_compiles_for_gfx950():
     header = os.path.join(ROOT, "include", "mw_rings.h")
     shared = os.path.join(build.CSRC, "mw_lib_host.h")                          # the host layer the device libraries include
     common = os.path.join(build.CSRC, "mw_common.hip.h")
-    assert set(build.RINGS_DEPS) == {build.RINGS_SRC, header, shared, common} and all(os.path.exists(p) for p in build.RINGS_DEPS)
+    cells = os.path.join(build.CSRC, "mw_lib_cells.h")                          # the cell grid, sort and walks; not a .hip.h, so not libmw_hip.so's
+    assert set(build.RINGS_DEPS) == {build.RINGS_SRC, header, shared, cells, common} and all(os.path.exists(p) for p in build.RINGS_DEPS)
+    assert cells not in build.DEPS and cells not in build.SK_DEPS
     for deps in (build.DEPS, build.SK_DEPS, build.BOO_DEPS, build.TET_DEPS, build.ADF_DEPS, build.COMMS_DEPS):   # no other library moves with it
         assert not any(p in deps for p in (build.RINGS_SRC, header))
     assert os.path.basename(build.RINGS_SRC) == "mw_rings.hip" and not any("ring" in f for f in os.listdir(build.CSRC) if f.endswith(".hip.h"))
@@ -116,7 +118,7 @@ def test_no_kernel_uses_scratch_memory_or_spills(tmp_path):
     seen = set()
     for blk in notes.split("- .agpr_count")[1:]:
         name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        m = re.match(r"_ZN7mwrings\d+(k_ring_[a-z0-9]+)(ILb[01]EE)?E", name)
+        m = re.match(r"_ZN7mwrings\d+(k_ring_[a-z0-9]+)(ILb[01]EE)?E", name) or re.match(r"_ZN7mwcells\d+(k_cells_[a-z]+)E", name)
         assert m, name                                                       # the library holds no other kernel
         get = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1))     # noqa: E731
         assert get("private_segment_fixed_size") == 0 and get("vgpr_spill_count") == 0 and get("sgpr_spill_count") == 0, name

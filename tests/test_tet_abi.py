@@ -14,7 +14,7 @@ import pytest
 from conftest import ROOT, load_golden
 
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-KERNELS = (b"k_tet_bin", b"k_tet_scan", b"k_tet_place", b"k_tet_rank", b"k_tet_select", b"k_tet_summary", b"k_tet_small")
+KERNELS = (b"k_cells_bin", b"k_cells_scan", b"k_cells_place", b"k_cells_rank", b"k_tet_select", b"k_tet_summary", b"k_tet_small")
 ANG_TO_BOHR = 1.0 / 0.5291772108
 
 
@@ -45,6 +45,8 @@ def test_build_tet_compiles_for_gfx950():
     for deps in (build.DEPS, build.SK_DEPS, build.BOO_DEPS, build.COMMS_DEPS):   # no other library moves with it
         assert not any(p in deps for p in (build.TET_SRC, header))
     assert shared not in build.DEPS
+    cells = os.path.join(build.CSRC, "mw_lib_cells.h")                          # the cell grid, sort and walks; not a .hip.h, so not libmw_hip.so's
+    assert cells in build.TET_DEPS and cells not in build.DEPS and cells not in build.SK_DEPS
     assert os.path.basename(build.TET_SRC) == "mw_tet.hip" and not any("tet" in f for f in os.listdir(build.CSRC) if f.endswith(".hip.h"))
 
 
@@ -110,7 +112,7 @@ def test_no_kernel_uses_scratch_memory_or_spills(tmp_path):
     seen = set()
     for blk in notes.split("- .agpr_count")[1:]:
         name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        m = re.match(r"_ZN5mwtet\d+(k_tet_[a-z0-9]+)E", name)
+        m = re.match(r"_ZN5mwtet\d+(k_tet_[a-z0-9]+)E", name) or re.match(r"_ZN7mwcells\d+(k_cells_[a-z]+)E", name)
         assert m, name                                                       # the library holds no other kernel
         get = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1))     # noqa: E731
         assert get("private_segment_fixed_size") == 0 and get("vgpr_spill_count") == 0 and get("sgpr_spill_count") == 0, name
