@@ -1,8 +1,8 @@
 """Build libmw_hip.so (the C-ABI engine), libmw_comms.so (the RCCL exchange layer for a Fortran host, include/mw_comms.h),
 libmw_sk.so (the structure factor S(k), include/mw_sk.h), libmw_boo.so (the Steinhardt bond-order parameters,
 include/mw_boo.h), libmw_tet.so (tetrahedral order, d5 and LSI from the sorted nearest neighbours, include/mw_tet.h),
-libmw_adf.so (the O-O-O angle distribution, include/mw_adf.h) and libmw_rings.so (the primitive rings of the bond network,
-include/mw_rings.h) in-tree with hipcc for gfx950.
+libmw_adf.so (the O-O-O angle distribution, include/mw_adf.h), libmw_rings.so (the primitive rings of the bond network,
+include/mw_rings.h) and libmw_quench.so (inherent-structure quenches, include/mw_quench.h) in-tree with hipcc for gfx950.
 
     python -m mc_water_ls_mw_amd.build [--force]
 
@@ -51,6 +51,10 @@ ADF_DEPS = [ADF_SRC, LIB_HOST, LIB_CELLS, os.path.join(CSRC, "mw_common.hip.h"),
 RINGS_LIB = os.path.join(PKG, "libmw_rings.so")
 RINGS_SRC = os.path.join(CSRC, "mw_rings.hip")
 RINGS_DEPS = [RINGS_SRC, LIB_HOST, LIB_CELLS, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_rings.h")]
+
+QUENCH_LIB = os.path.join(PKG, "libmw_quench.so")
+QUENCH_SRC = os.path.join(CSRC, "mw_quench.hip")
+QUENCH_DEPS = [QUENCH_SRC, LIB_HOST, LIB_CELLS, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_quench.h")]
 
 
 def hipcc_path():
@@ -116,7 +120,12 @@ def build_rings(force=False, verbose=False):
     return _compile(RINGS_LIB, [RINGS_SRC], RINGS_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
 
 
+def build_quench(force=False, verbose=False):
+    """libmw_quench.so: the FIRE quench kernels and their C ABI, a translation unit of its own like libmw_rings.so."""
+    return _compile(QUENCH_LIB, [QUENCH_SRC], QUENCH_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
+
+
 if __name__ == "__main__":
     force = "--force" in sys.argv
-    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf, build_rings):
+    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf, build_rings, build_quench):
         print(builder(force=force, verbose=True))

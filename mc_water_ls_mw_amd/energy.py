@@ -546,6 +546,20 @@ class EnergyModule:
         self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
         return rings.ring_statistics(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, r_cut_ang, list_cap)
 
+    # -- inherent structures (libmw_quench.so, include/mw_quench.h; no counterpart in the reference) -----------------
+    def inherent_structures(self, first_ils=1, count=None, ftol=1e-8, max_iter=10000, fire=None):
+        """(pos_out [count, nwater, 3], forces [count, nwater, 3], stats [count, 6], iters [count, 2]) of ``count`` boxes --
+        quench.inherent_structures -- from the positions the DEVICE holds and this module's hmatrix (after device volume
+        moves call ``WalkerFarm.sync_cells`` first).  The positions take one host hop (mw_download_positions_range) on their
+        way to libmw_quench.so, which shares nothing with the engine but the device; the engine's own positions stay as
+        they are."""
+        from . import quench
+        count = self.num_lattices - first_ils + 1 if count is None else count
+        self._ils(first_ils), self._ils(first_ils + count - 1)
+        pos = np.zeros((count, self.nwater, 3))
+        self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
+        return quench.inherent_structures(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, ftol, max_iter, fire)
+
     def model_energy_counts(self, ils):
         p, t = ctypes.c_longlong(0), ctypes.c_longlong(0)
         self._chk(self.L.mw_model_energy_counts(ils, ctypes.byref(p), ctypes.byref(t)))

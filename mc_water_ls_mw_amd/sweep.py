@@ -402,6 +402,24 @@ class WalkerFarm:
         shape = (self.nwalkers, self.nlat)
         return hist.reshape(*shape, 5), six.reshape(shape), summary[:, 0].reshape(shape)
 
+    def inherent_structures(self, ftol=1e-8, max_iter=10000, fire=None):
+        """(pos_out [nwalkers, nlat, nwater, 3], stats [nwalkers, nlat, 6], iters [nwalkers, nlat, 2]): the inherent structure
+        of every lattice of every walker -- the local minimum of the mW energy below its configuration at fixed cell
+        (include/mw_quench.h) --, stats = (E at the start, E at the end in Hartree, the largest |F| component at the start
+        and at the end in Hartree / bohr, the largest and the rms displacement in bohr) and iters = (iterations, converged),
+        from the positions and cells the device holds (the cells read back through :meth:`sync_cells` first).  The walkers'
+        own configurations are left alone.  The quenched positions are plain positions and go straight into the analysis
+        libraries, which take such; the LSI, bimodal only on the inherent structure::
+
+            pos_is, stats, iters = farm.inherent_structures(ftol=1e-8)
+            order, _, _, summary = tetrahedral.tetrahedral_order(farm.sync_cells(), pos_is.reshape(-1, farm.em.nwater, 3))
+            lsi = order[:, :, 3]                                   # bohr^2, per molecule of every quenched box
+        """
+        self.sync_cells()
+        pos_out, _, stats, iters = self.em.inherent_structures(1, self.em.num_lattices, ftol, max_iter, fire)
+        shape = (self.nwalkers, self.nlat)
+        return pos_out.reshape(*shape, self.em.nwater, 3), stats.reshape(*shape, 6), iters.reshape(*shape, 2)
+
     # -- chain synchronisation (mc_check_chain_synchronisation, mc_moves.F90:2217-2416) -------------------------
     def set_reference(self):
         """Remember the reference configuration (ref_hmatrix / ref_ljr of init.f90:90,106) from the host's current
