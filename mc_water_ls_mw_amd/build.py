@@ -2,7 +2,8 @@
 libmw_sk.so (the structure factor S(k), include/mw_sk.h), libmw_boo.so (the Steinhardt bond-order parameters,
 include/mw_boo.h), libmw_tet.so (tetrahedral order, d5 and LSI from the sorted nearest neighbours, include/mw_tet.h),
 libmw_adf.so (the O-O-O angle distribution, include/mw_adf.h), libmw_rings.so (the primitive rings of the bond network,
-include/mw_rings.h) and libmw_quench.so (inherent-structure quenches, include/mw_quench.h) in-tree with hipcc for gfx950.
+include/mw_rings.h), libmw_quench.so (inherent-structure quenches, include/mw_quench.h) and libmw_md.so (molecular dynamics,
+include/mw_md.h) in-tree with hipcc for gfx950.
 
     python -m mc_water_ls_mw_amd.build [--force]
 
@@ -55,6 +56,12 @@ RINGS_DEPS = [RINGS_SRC, LIB_HOST, LIB_CELLS, os.path.join(CSRC, "mw_common.hip.
 QUENCH_LIB = os.path.join(PKG, "libmw_quench.so")
 QUENCH_SRC = os.path.join(CSRC, "mw_quench.hip")
 QUENCH_DEPS = [QUENCH_SRC, LIB_HOST, LIB_CELLS, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_quench.h")]
+LIB_FORCES = os.path.join(CSRC, "mw_lib_forces.h")   # the moments, the entry force and the fixed-order reductions libmw_quench.so and libmw_md.so share
+QUENCH_BUILD_DEPS = [*QUENCH_DEPS, LIB_FORCES]       # what build_quench watches: the library's own files and the shared force layer
+
+MD_LIB = os.path.join(PKG, "libmw_md.so")
+MD_SRC = os.path.join(CSRC, "mw_md.hip")
+MD_DEPS = [MD_SRC, LIB_HOST, LIB_CELLS, LIB_FORCES, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_md.h")]
 
 
 def hipcc_path():
@@ -122,10 +129,16 @@ def build_rings(force=False, verbose=False):
 
 def build_quench(force=False, verbose=False):
     """libmw_quench.so: the FIRE quench kernels and their C ABI, a translation unit of its own like libmw_rings.so."""
-    return _compile(QUENCH_LIB, [QUENCH_SRC], QUENCH_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
+    return _compile(QUENCH_LIB, [QUENCH_SRC], QUENCH_BUILD_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
+
+
+def build_md(force=False, verbose=False):
+    """libmw_md.so: the molecular-dynamics kernels and their C ABI, a translation unit of its own like libmw_quench.so, whose
+    force layer (mw_lib_forces.h) it shares."""
+    return _compile(MD_LIB, [MD_SRC], MD_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
 
 
 if __name__ == "__main__":
     force = "--force" in sys.argv
-    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf, build_rings, build_quench):
+    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf, build_rings, build_md, build_quench):
         print(builder(force=force, verbose=True))

@@ -560,6 +560,20 @@ class EnergyModule:
         self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
         return quench.inherent_structures(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, ftol, max_iter, fire)
 
+    # -- molecular dynamics (libmw_md.so, include/mw_md.h; no counterpart in the reference) --------------------------
+    def molecular_dynamics(self, first_ils=1, count=None, nsteps=0, dt=1.0, **kwargs):
+        """(pos_out, vel_out, forces [count, nwater, 3], trace [count, nsteps // sample_every + 1, 4], status [count, 2]) of
+        ``count`` boxes -- dynamics.molecular_dynamics, which takes the keywords (kT, gamma, vel, mass, seed, streams, step0,
+        sample_every, pos_ref) -- from the positions the DEVICE holds and this module's hmatrix (after device volume moves
+        call ``WalkerFarm.sync_cells`` first).  The positions take one host hop (mw_download_positions_range) on their way to
+        libmw_md.so, which shares nothing with the engine but the device; the engine's own positions stay as they are."""
+        from . import dynamics
+        count = self.num_lattices - first_ils + 1 if count is None else count
+        self._ils(first_ils), self._ils(first_ils + count - 1)
+        pos = np.zeros((count, self.nwater, 3))
+        self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
+        return dynamics.molecular_dynamics(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, nsteps, dt, **kwargs)
+
     def model_energy_counts(self, ils):
         p, t = ctypes.c_longlong(0), ctypes.c_longlong(0)
         self._chk(self.L.mw_model_energy_counts(ils, ctypes.byref(p), ctypes.byref(t)))

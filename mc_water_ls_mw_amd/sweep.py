@@ -420,6 +420,25 @@ class WalkerFarm:
         shape = (self.nwalkers, self.nlat)
         return pos_out.reshape(*shape, self.em.nwater, 3), stats.reshape(*shape, 6), iters.reshape(*shape, 2)
 
+    def molecular_dynamics(self, nsteps, dt, first_global_walker=0, **kwargs):
+        """(pos_out, vel_out [nwalkers, nlat, nwater, 3], trace [nwalkers, nlat, nsteps // sample_every + 1, 4], status
+        [nwalkers, nlat, 2]): ``nsteps`` BAOAB steps of ``dt`` (include/mw_md.h) from the configuration of every lattice of
+        every walker, with the keywords of dynamics.molecular_dynamics (kT, gamma, vel [nwalkers * nlat, nwater, 3], mass,
+        seed, step0, sample_every, pos_ref), from the positions and cells the device holds (the cells read back through
+        :meth:`sync_cells` first).  The noise stream of lattice l of walker w (both from 0) is (``first_global_walker`` + w)
+        * nlat + l -- with ``first_global_walker`` the number of walkers on the ranks before this one, a walker's
+        trajectory does not depend on how the walkers are split over ranks.  The walkers' own configurations are left alone:
+        thermalised, decorrelated starting configurations come out as plain positions."""
+        if "streams" in kwargs:
+            raise ValueError("the farm names the noise streams itself: (first_global_walker + walker) * nlat + lattice")
+        self.sync_cells()
+        nb = self.em.num_lattices
+        streams = np.uint64(int(first_global_walker) * self.nlat) + np.arange(nb, dtype=np.uint64)
+        pos_out, vel_out, _, trace, status = self.em.molecular_dynamics(1, nb, nsteps, dt, streams=streams, **kwargs)
+        shape = (self.nwalkers, self.nlat)
+        return (pos_out.reshape(*shape, self.em.nwater, 3), vel_out.reshape(*shape, self.em.nwater, 3), trace.reshape(*shape, -1, 4),
+                status.reshape(*shape, 2))
+
     # -- chain synchronisation (mc_check_chain_synchronisation, mc_moves.F90:2217-2416) -------------------------
     def set_reference(self):
         """Remember the reference configuration (ref_hmatrix / ref_ljr of init.f90:90,106) from the host's current
