@@ -2,8 +2,8 @@
 libmw_sk.so (the structure factor S(k), include/mw_sk.h), libmw_boo.so (the Steinhardt bond-order parameters,
 include/mw_boo.h), libmw_tet.so (tetrahedral order, d5 and LSI from the sorted nearest neighbours, include/mw_tet.h),
 libmw_adf.so (the O-O-O angle distribution, include/mw_adf.h), libmw_rings.so (the primitive rings of the bond network,
-include/mw_rings.h), libmw_quench.so (inherent-structure quenches, include/mw_quench.h) and libmw_md.so (molecular dynamics,
-include/mw_md.h) in-tree with hipcc for gfx950.
+include/mw_rings.h), libmw_quench.so (inherent-structure quenches, include/mw_quench.h), libmw_md.so (molecular dynamics,
+include/mw_md.h) and libmw_npt.so (molecular dynamics at constant pressure, include/mw_npt.h) in-tree with hipcc for gfx950.
 
     python -m mc_water_ls_mw_amd.build [--force]
 
@@ -56,12 +56,16 @@ RINGS_DEPS = [RINGS_SRC, LIB_HOST, LIB_CELLS, os.path.join(CSRC, "mw_common.hip.
 QUENCH_LIB = os.path.join(PKG, "libmw_quench.so")
 QUENCH_SRC = os.path.join(CSRC, "mw_quench.hip")
 QUENCH_DEPS = [QUENCH_SRC, LIB_HOST, LIB_CELLS, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_quench.h")]
-LIB_FORCES = os.path.join(CSRC, "mw_lib_forces.h")   # the moments, the entry force and the fixed-order reductions libmw_quench.so and libmw_md.so share
+LIB_FORCES = os.path.join(CSRC, "mw_lib_forces.h")   # the moments, the entry force and virial and the fixed-order reductions libmw_quench.so, libmw_md.so and libmw_npt.so share
 QUENCH_BUILD_DEPS = [*QUENCH_DEPS, LIB_FORCES]       # what build_quench watches: the library's own files and the shared force layer
 
 MD_LIB = os.path.join(PKG, "libmw_md.so")
 MD_SRC = os.path.join(CSRC, "mw_md.hip")
 MD_DEPS = [MD_SRC, LIB_HOST, LIB_CELLS, LIB_FORCES, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_md.h")]
+
+NPT_LIB = os.path.join(PKG, "libmw_npt.so")
+NPT_SRC = os.path.join(CSRC, "mw_npt.hip")
+NPT_DEPS = [NPT_SRC, LIB_HOST, LIB_CELLS, LIB_FORCES, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_npt.h")]
 
 
 def hipcc_path():
@@ -138,7 +142,13 @@ def build_md(force=False, verbose=False):
     return _compile(MD_LIB, [MD_SRC], MD_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
 
 
+def build_npt(force=False, verbose=False):
+    """libmw_npt.so: the constant-pressure molecular-dynamics kernels and their C ABI, a translation unit of its own like
+    libmw_md.so, whose force layer (mw_lib_forces.h, with the virial) it shares."""
+    return _compile(NPT_LIB, [NPT_SRC], NPT_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
+
+
 if __name__ == "__main__":
     force = "--force" in sys.argv
-    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf, build_rings, build_md, build_quench):
+    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf, build_rings, build_md, build_npt, build_quench):
         print(builder(force=force, verbose=True))

@@ -1,7 +1,8 @@
-// The force layer the inherent-structure quenches and the molecular dynamics (mw_md.hip) share: a molecule's
+// The force layer the inherent-structure quenches and the molecular dynamics (mw_md.hip, mw_npt.hip) share: a molecule's
 // moments and energy (Sums), the derivative of its triplet sum against a centre's moments (triplet_grad), the force one entry
-// puts on it (entry_force), the cell held in vector registers (CellRegs / in_vgpr) and the reductions in a fixed order (the DPP
-// trees of a wavefront, block_reduce over the wavefronts of a workgroup).  Device code only, all of it inlined: every library
+// puts on it (entry_force) and that entry's share of the scalar virial (entry_virial, used by mw_npt.hip alone), the cell held
+// in vector registers (CellRegs / in_vgpr) and the reductions in a fixed order (the DPP trees of a wavefront, block_reduce over
+// the wavefronts of a workgroup).  Device code only, all of it inlined: every library
 // compiles it into its own kernels and exports nothing from here.  Included after `#pragma clang fp contract(off)`, after
 // mw_common.hip.h and after mw_lib_cells.h (block_reduce is written for its kThreads).  The derivatives are those of
 // mw_forces.hip.h, written again here: these libraries share mw_common.hip.h with the engine and nothing else.
@@ -95,6 +96,22 @@ __device__ __forceinline__ void entry_force(const double (&Mi)[kMom], const doub
     fy = fy + __builtin_fma(mw::kLamEps, ty + sy, dphi * uy);
     fz = fz + __builtin_fma(mw::kLamEps, tz + sz, dphi * uz);
 }
+
+// entry_force, and the entry's share of the scalar virial W = tr of the engine's virial = -3 V dE/dV (mw_energy.h; the pressure
+// is (2 K + W) / (3 V)).  e, the force of this entry alone, is entry_force's term from zeroed sums, so f gets the bits entry_force
+// gives it; dw = dw + d . e.  Every pair (i, entry k) has its mirror (j, entry -d), and e holds both the derivative of the centre's
+// own energy against d and that of the neighbour's against -d, so the sum of d . e over all entries of a box counts every
+// d . dE/dd twice with the sign of a force: W of the box = -1/2 the sum of the lanes' dw (lane_virial), each lane in the order of
+// its walk.  An image of the molecule itself is skipped by the walks' callers: the cell rule keeps it beyond the cutoff.
+__device__ __forceinline__ void entry_virial(const double (&Mi)[kMom], const double (&Mj)[kMom], double r2, double dx, double dy, double dz,
+                                             double& fx, double& fy, double& fz, double& dw)
+{
+    double ex = 0.0, ey = 0.0, ez = 0.0;
+    entry_force(Mi, Mj, r2, dx, dy, dz, ex, ey, ez);
+    fx = fx + ex; fy = fy + ey; fz = fz + ez;
+    dw = dw + __builtin_fma(dx, ex, __builtin_fma(dy, ey, dz * ez));
+}
+__device__ __forceinline__ double lane_virial(double dw) { return -0.5 * dw; }
 
 // The cell's nine doubles held in vector registers.  Left to itself the compiler keeps them in 18 scalar registers next to the
 // scalar constants of pair_terms' polynomial, and the walks of the force pass then run out of scalar registers and spill.

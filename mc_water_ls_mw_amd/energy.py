@@ -574,6 +574,20 @@ class EnergyModule:
         self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
         return dynamics.molecular_dynamics(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, nsteps, dt, **kwargs)
 
+    # -- molecular dynamics at constant pressure (libmw_npt.so, include/mw_npt.h) ---------------------------------------
+    def molecular_dynamics_npt(self, first_ils=1, count=None, nsteps=0, dt=1.0, **kwargs):
+        """(pos_out, vel_out, forces, cells_out [count, 3, 3], ref_out, trace [count, nsteps // sample_every + 1, 6], status
+        [count, 2]) of ``count`` boxes -- npt.molecular_dynamics_npt, which takes the keywords (pressure, kT, gamma, tau_p,
+        beta_T, baro_every, vel, mass, seed, streams, step0, sample_every, pos_ref) -- from the positions the DEVICE holds and
+        this module's hmatrix, as :meth:`molecular_dynamics` takes them; the engine's own positions and cells stay as they
+        are."""
+        from . import npt
+        count = self.num_lattices - first_ils + 1 if count is None else count
+        self._ils(first_ils), self._ils(first_ils + count - 1)
+        pos = np.zeros((count, self.nwater, 3))
+        self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
+        return npt.molecular_dynamics_npt(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, nsteps, dt, **kwargs)
+
     def model_energy_counts(self, ils):
         p, t = ctypes.c_longlong(0), ctypes.c_longlong(0)
         self._chk(self.L.mw_model_energy_counts(ils, ctypes.byref(p), ctypes.byref(t)))

@@ -439,6 +439,23 @@ class WalkerFarm:
         return (pos_out.reshape(*shape, self.em.nwater, 3), vel_out.reshape(*shape, self.em.nwater, 3), trace.reshape(*shape, -1, 4),
                 status.reshape(*shape, 2))
 
+    def molecular_dynamics_npt(self, nsteps, dt, first_global_walker=0, **kwargs):
+        """(pos_out, vel_out [nwalkers, nlat, nwater, 3], cells_out [nwalkers, nlat, 3, 3], trace [nwalkers, nlat, nsteps //
+        sample_every + 1, 6], status [nwalkers, nlat, 2]): :meth:`molecular_dynamics` at constant pressure (include/mw_npt.h),
+        with the keywords of npt.molecular_dynamics_npt (``pressure`` defaults to the farm's own, then kT, gamma, tau_p,
+        beta_T, baro_every, vel, mass, seed, step0, sample_every, pos_ref) and the same noise streams.  The cells come out too:
+        every box ends in a cell of its own.  The walkers' own configurations and cells are left alone."""
+        if "streams" in kwargs:
+            raise ValueError("the farm names the noise streams itself: (first_global_walker + walker) * nlat + lattice")
+        self.sync_cells()
+        nb = self.em.num_lattices
+        streams = np.uint64(int(first_global_walker) * self.nlat) + np.arange(nb, dtype=np.uint64)
+        kwargs.setdefault("pressure", self.pressure)
+        pos_out, vel_out, _, cells_out, _, trace, status = self.em.molecular_dynamics_npt(1, nb, nsteps, dt, streams=streams, **kwargs)
+        shape = (self.nwalkers, self.nlat)
+        return (pos_out.reshape(*shape, self.em.nwater, 3), vel_out.reshape(*shape, self.em.nwater, 3), cells_out.reshape(*shape, 3, 3),
+                trace.reshape(*shape, -1, 6), status.reshape(*shape, 2))
+
     # -- chain synchronisation (mc_check_chain_synchronisation, mc_moves.F90:2217-2416) -------------------------
     def set_reference(self):
         """Remember the reference configuration (ref_hmatrix / ref_ljr of init.f90:90,106) from the host's current
