@@ -3,7 +3,8 @@ libmw_sk.so (the structure factor S(k), include/mw_sk.h), libmw_boo.so (the Stei
 include/mw_boo.h), libmw_tet.so (tetrahedral order, d5 and LSI from the sorted nearest neighbours, include/mw_tet.h),
 libmw_adf.so (the O-O-O angle distribution, include/mw_adf.h), libmw_rings.so (the primitive rings of the bond network,
 include/mw_rings.h), libmw_quench.so (inherent-structure quenches, include/mw_quench.h), libmw_md.so (molecular dynamics,
-include/mw_md.h) and libmw_npt.so (molecular dynamics at constant pressure, include/mw_npt.h) in-tree with hipcc for gfx950.
+include/mw_md.h), libmw_npt.so (molecular dynamics at constant pressure, include/mw_npt.h) and libmw_tcf.so (time correlation
+functions of trajectories, include/mw_tcf.h) in-tree with hipcc for gfx950.
 
     python -m mc_water_ls_mw_amd.build [--force]
 
@@ -66,6 +67,10 @@ MD_DEPS = [MD_SRC, LIB_HOST, LIB_CELLS, LIB_FORCES, os.path.join(CSRC, "mw_commo
 NPT_LIB = os.path.join(PKG, "libmw_npt.so")
 NPT_SRC = os.path.join(CSRC, "mw_npt.hip")
 NPT_DEPS = [NPT_SRC, LIB_HOST, LIB_CELLS, LIB_FORCES, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_npt.h")]
+
+TCF_LIB = os.path.join(PKG, "libmw_tcf.so")
+TCF_SRC = os.path.join(CSRC, "mw_tcf.hip")
+TCF_DEPS = [TCF_SRC, LIB_HOST, os.path.join(os.path.dirname(PKG), "include", "mw_tcf.h")]   # no cell grid and no shared device header
 
 
 def hipcc_path():
@@ -148,7 +153,13 @@ def build_npt(force=False, verbose=False):
     return _compile(NPT_LIB, [NPT_SRC], NPT_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
 
 
+def build_tcf(force=False, verbose=False):
+    """libmw_tcf.so: the time-correlation kernels and their C ABI, a translation unit of its own over the libraries' host layer
+    alone (it sorts nothing into cells)."""
+    return _compile(TCF_LIB, [TCF_SRC], TCF_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
+
+
 if __name__ == "__main__":
     force = "--force" in sys.argv
-    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf, build_rings, build_md, build_npt, build_quench):
+    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf, build_rings, build_md, build_npt, build_tcf, build_quench):
         print(builder(force=force, verbose=True))

@@ -173,3 +173,57 @@ def molecular_dynamics_torch(cells_t, pos_t, nsteps, dt, kT=0.0, gamma=0.0, vel_
                                 int(nsteps), int(sample_every), float(dt), float(mass), float(kT), float(gamma), pos_out.data_ptr(),
                                 vel_out.data_ptr(), forces.data_ptr(), trace.data_ptr(), status.data_ptr()))
     return pos_out, vel_out, forces, trace, status
+
+
+def trajectory(cells_t, pos_t, nframes, steps_per_frame, dt, sample_every=1, **md_keywords):
+    """(frames [nframes, nboxes, nwater, 3], vel_frames [nframes, nboxes, nwater, 3], trace [nboxes, (nframes - 1) *
+    steps_per_frame // sample_every + 1, 4], status [nboxes, 2]) as device tensors: a recorded run of (``nframes`` - 1) *
+    ``steps_per_frame`` steps of ``dt`` from ``pos_t``, one frame every ``steps_per_frame`` steps, frame 0 being the input
+    (``vel_t``: None for zero velocities).  The frames are what ``timecorr.time_correlations_torch`` takes.
+
+    The run is ``nframes`` - 1 chained :func:`molecular_dynamics_torch` calls -- ``pos_ref_t`` the first positions (or the one
+    given), ``step0`` advanced by the steps done -- so by the contract of include/mw_md.h every frame is byte for byte what one
+    uninterrupted run holds at that step, the last frame that run's ``pos_out``, and the trace its trace.  The keywords are
+    those of molecular_dynamics_torch (kT, gamma, vel_t, mass, seed, streams_t, step0, pos_ref_t); ``sample_every`` must divide
+    ``steps_per_frame``.  A box that freezes (status [b, 1] = 1, status [b, 0] = the steps it completed) repeats its frozen
+    state in every later frame and its last trace row in every later row."""
+    import torch
+    nframes, spf, sample_every = int(nframes), int(steps_per_frame), int(sample_every)
+    if nframes < 1 or spf < 1 or sample_every < 1 or spf % sample_every:
+        raise MwError(f"trajectory: nframes = {nframes}, steps_per_frame = {spf}, sample_every = {sample_every}: expected nframes >= 1 and "
+                      f"sample_every >= 1 dividing steps_per_frame >= 1")
+    kw = dict(md_keywords)
+    for name in ("nsteps",):
+        if name in kw:
+            raise MwError(f"trajectory: {name} is set by nframes and steps_per_frame")
+    vel_t, step0 = kw.pop("vel_t", None), int(kw.pop("step0", 0))
+    pos_ref_t = kw.pop("pos_ref_t", None)
+    check_device_tensors((cells_t, torch.float64, "cells_t"), (pos_t, torch.float64, "pos_t"))
+    check_boxes(cells_t, pos_t)
+    nb, n = pos_t.shape[0], pos_t.shape[1]
+    frames = torch.zeros((nframes, nb, n, 3), dtype=torch.float64, device=pos_t.device)
+    vel_frames = torch.zeros_like(frames)
+    frames[0] = pos_t
+    if vel_t is not None:
+        vel_frames[0] = vel_t
+    pos_ref_t = frames[0].clone() if pos_ref_t is None else pos_ref_t
+    rows = spf // sample_every
+    trace = torch.zeros((nb, (nframes - 1) * rows + 1, 4), dtype=torch.float64, device=pos_t.device)
+    status = torch.zeros((nb, 2), dtype=torch.int32, device=pos_t.device)
+    for f in range(1, nframes):
+        p, v, _, tr, st = molecular_dynamics_torch(cells_t, frames[f - 1], spf, dt, vel_t=vel_frames[f - 1], step0=step0 + (f - 1) * spf,
+                                                   sample_every=sample_every, pos_ref_t=pos_ref_t, **kw)
+        was = status[:, 1] != 0                                              # frozen in an earlier call: its state and its row repeat
+        frames[f] = torch.where(was[:, None, None], frames[f - 1], p)
+        vel_frames[f] = torch.where(was[:, None, None], vel_frames[f - 1], v)
+        r0 = (f - 1) * rows
+        if f == 1:
+            trace[:, 0] = tr[:, 0]
+        trace[:, r0 + 1:r0 + rows + 1] = torch.where(was[:, None, None], trace[:, r0:r0 + 1].expand(-1, rows, -1), tr[:, 1:])
+        status[:, 0] += torch.where(was, torch.zeros_like(st[:, 0]), st[:, 0])
+        status[:, 1] = torch.where(was, status[:, 1], st[:, 1])
+    if nframes == 1:
+        _, _, _, tr, st = molecular_dynamics_torch(cells_t, frames[0], 0, dt, vel_t=vel_frames[0], step0=step0, sample_every=sample_every,
+                                                   pos_ref_t=pos_ref_t, **kw)
+        trace[:, 0], status = tr[:, 0], st
+    return frames, vel_frames, trace, status

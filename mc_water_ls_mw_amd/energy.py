@@ -588,6 +588,35 @@ class EnergyModule:
         self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
         return npt.molecular_dynamics_npt(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, nsteps, dt, **kwargs)
 
+    # -- time correlation functions (libmw_md.so records, libmw_tcf.so correlates; include/mw_tcf.h) ---------------------
+    def time_correlations(self, first_ils=1, count=None, nframes=2, steps_per_frame=1, dt=1.0, nlags=None, origin_every=1, q=None, edges=None,
+                          hist_lags=(), remove_com=False, with_vacf=True, **md_keywords):
+        """((msd, mqd, vacf, fs, hist), status [count, 2]) of ``count`` boxes: a recorded molecular-dynamics run of ``nframes``
+        frames, ``steps_per_frame`` steps of ``dt`` apart (dynamics.trajectory with the keywords kT, gamma, vel, mass, seed,
+        streams, step0), from the positions the DEVICE holds and this module's hmatrix, and its time correlation functions
+        (timecorr.time_correlations_torch: per box and lag, host arrays; ``with_vacf=False`` leaves the velocities out).  The
+        positions take one host hop (mw_download_positions_range), as :meth:`molecular_dynamics` takes them; the engine's own
+        positions stay as they are."""
+        import torch
+        from . import dynamics, timecorr
+        count = self.num_lattices - first_ils + 1 if count is None else count
+        self._ils(first_ils), self._ils(first_ils + count - 1)
+        pos = np.zeros((count, self.nwater, 3))
+        self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
+        dev = torch.device("cuda", dynamics._dev.device or 0)
+        up = lambda a, dtype=torch.float64: torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(dev).contiguous()   # noqa: E731
+        kw = dict(md_keywords)
+        if kw.get("vel") is not None:
+            kw["vel_t"] = up(np.asarray(kw["vel"], dtype=np.float64).reshape(count, self.nwater, 3))
+        kw.pop("vel", None)
+        if kw.get("streams") is not None:
+            kw["streams_t"] = up(np.ascontiguousarray(kw["streams"], dtype=np.uint64).view(np.int64), torch.int64)
+        kw.pop("streams", None)
+        cells_t = up(self.hmatrix[first_ils - 1:first_ils - 1 + count])
+        frames, vel_frames, _, status = dynamics.trajectory(cells_t, up(pos), nframes, steps_per_frame, dt, **kw)
+        out = timecorr.time_correlations_torch(frames, vel_frames if with_vacf else None, nlags, origin_every, q, edges, hist_lags, remove_com)
+        return tuple(None if t is None else t.cpu().numpy() for t in out), status.cpu().numpy()
+
     def model_energy_counts(self, ils):
         p, t = ctypes.c_longlong(0), ctypes.c_longlong(0)
         self._chk(self.L.mw_model_energy_counts(ils, ctypes.byref(p), ctypes.byref(t)))

@@ -456,6 +456,26 @@ class WalkerFarm:
         return (pos_out.reshape(*shape, self.em.nwater, 3), vel_out.reshape(*shape, self.em.nwater, 3), cells_out.reshape(*shape, 3, 3),
                 trace.reshape(*shape, -1, 6), status.reshape(*shape, 2))
 
+    def time_correlations(self, nframes, steps_per_frame, dt, first_global_walker=0, **kwargs):
+        """(msd, mqd, vacf [nlat, nlags], fs [nlat, nlags, nq], hist [nlat, nh, nedges + 1], status [nwalkers, nlat, 2]): the time
+        correlation functions (include/mw_tcf.h) of a recorded molecular-dynamics run of ``nframes`` frames, ``steps_per_frame``
+        steps of ``dt`` apart, from the configuration of every lattice of every walker, averaged over the walkers per lattice
+        (the histograms are summed: they are counts) -- with the keywords of ``EnergyModule.time_correlations`` (nlags,
+        origin_every, q, edges, hist_lags, remove_com, with_vacf, kT, gamma, vel, mass, seed, step0).  The noise stream of lattice l
+        of walker w is (``first_global_walker`` + w) * nlat + l, as in :meth:`molecular_dynamics`: a walker's curves do not depend
+        on how the walkers are split.  The walkers' own configurations are left alone.  A result nobody asked for is None."""
+        if "streams" in kwargs:
+            raise ValueError("the farm names the noise streams itself: (first_global_walker + walker) * nlat + lattice")
+        self.sync_cells()
+        nb = self.em.num_lattices
+        streams = np.uint64(int(first_global_walker) * self.nlat) + np.arange(nb, dtype=np.uint64)
+        curves, status = self.em.time_correlations(1, nb, nframes, steps_per_frame, dt, streams=streams, **kwargs)
+        shape = (self.nwalkers, self.nlat)
+        mean = lambda a: None if a is None else a.reshape(*shape, *a.shape[1:]).mean(axis=0)     # noqa: E731
+        msd, mqd, vacf, fs, hist = curves
+        return (mean(msd), mean(mqd), mean(vacf), mean(fs), None if hist is None else hist.reshape(*shape, *hist.shape[1:]).sum(axis=0),
+                status.reshape(*shape, 2))
+
     # -- chain synchronisation (mc_check_chain_synchronisation, mc_moves.F90:2217-2416) -------------------------
     def set_reference(self):
         """Remember the reference configuration (ref_hmatrix / ref_ljr of init.f90:90,106) from the host's current
