@@ -560,6 +560,26 @@ class EnergyModule:
         self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
         return quench.inherent_structures(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, ftol, max_iter, fire)
 
+    # -- the Hessian and normal modes (libmw_hess.so, include/mw_hess.h; no counterpart in the reference) --------------
+    def hessian(self, ils):
+        """(H [3 nwater, 3 nwater], ef [2]) of box ``ils`` (from 1) -- phonons.hessian: the Gamma-point Hessian in Hartree /
+        bohr^2 and beside it the energy and the largest |F| component -- from the positions the DEVICE holds and this
+        module's hmatrix (after device volume moves call ``WalkerFarm.sync_cells`` first).  The positions take one host hop
+        (mw_download_positions_range) on their way to libmw_hess.so, which shares nothing with the engine but the device."""
+        from . import phonons
+        self._ils(ils)
+        pos = np.zeros((1, self.nwater, 3))
+        self._chk(self.L.mw_download_positions_range(ils, 1, _d(pos)))
+        return phonons.hessian(self.hmatrix[ils - 1], pos[0])
+
+    def normal_modes(self, ils, mass=None, vectors=False):
+        """phonons.normal_modes of :meth:`hessian` of box ``ils``: the signed frequencies in ascending order (negative: an
+        unstable direction -- the instantaneous normal modes of a configuration that is not a minimum), with ``vectors`` the
+        eigenvectors too.  ``mass`` defaults to phonons.MASS_WATER."""
+        from . import phonons
+        H, _ = self.hessian(ils)
+        return phonons.normal_modes(H, phonons.MASS_WATER if mass is None else mass, vectors)
+
     # -- molecular dynamics (libmw_md.so, include/mw_md.h; no counterpart in the reference) --------------------------
     def molecular_dynamics(self, first_ils=1, count=None, nsteps=0, dt=1.0, **kwargs):
         """(pos_out, vel_out, forces [count, nwater, 3], trace [count, nsteps // sample_every + 1, 4], status [count, 2]) of

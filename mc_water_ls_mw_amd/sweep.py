@@ -420,6 +420,33 @@ class WalkerFarm:
         shape = (self.nwalkers, self.nlat)
         return pos_out.reshape(*shape, self.em.nwater, 3), stats.reshape(*shape, 6), iters.reshape(*shape, 2)
 
+    def harmonic_free_energies(self, kT, ftol=1e-10, max_iter=10000, quantum=False):
+        """(e_min [nwalkers, nlat], f_vib [nwalkers, nlat], negative [nwalkers, nlat], converged [nwalkers, nlat], f_harm [nlat]):
+        the harmonic free energy of every lattice of every walker.  Every box is quenched to its inherent structure
+        (:meth:`inherent_structures`, include/mw_quench.h) and the dense Hessian is taken there (include/mw_hess.h); e_min is
+        the energy of the minimum in Hartree, f_vib = phonons.harmonic_free_energy of its normal modes at ``kT`` (Hartree)
+        without the three translations (NaN where a kept mode is not positive: the quench has not reached a minimum),
+        negative the number of eigenvalues below minus the three smallest in size, converged the quench's flag, and f_harm
+        the mean of e_min + f_vib over the walkers of each lattice: f_harm[1] - f_harm[0] is the harmonic estimate to hold
+        beside the lattice-switch free-energy difference.  The walkers' own configurations are left alone."""
+        from . import phonons
+        pos, stats, iters = self.inherent_structures(ftol, max_iter)
+        cells = np.asarray(self.em.hmatrix, dtype=np.float64)
+        n = self.em.nwater
+        H, _ = phonons.hessian(cells, pos.reshape(-1, n, 3))
+        shape = (self.nwalkers, self.nlat)
+        f_vib = np.full(self.em.num_lattices, np.nan)
+        negative = np.zeros(self.em.num_lattices, dtype=np.int64)
+        for b in range(self.em.num_lattices):
+            omega = phonons.normal_modes(H[b])
+            keep = omega[np.argsort(np.abs(omega), kind="stable")[3:]]
+            negative[b] = int((keep < 0.0).sum())
+            if keep.size == 0 or keep.min() > 0.0:
+                f_vib[b] = phonons.harmonic_free_energy(omega, kT, quantum)
+        e_min = stats[:, :, 1]
+        f_vib = f_vib.reshape(shape)
+        return e_min, f_vib, negative.reshape(shape), iters[:, :, 1].astype(bool), (e_min + f_vib).mean(axis=0)
+
     def molecular_dynamics(self, nsteps, dt, first_global_walker=0, **kwargs):
         """(pos_out, vel_out [nwalkers, nlat, nwater, 3], trace [nwalkers, nlat, nsteps // sample_every + 1, 4], status
         [nwalkers, nlat, 2]): ``nsteps`` BAOAB steps of ``dt`` (include/mw_md.h) from the configuration of every lattice of
