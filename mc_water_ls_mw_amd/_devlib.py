@@ -1,5 +1,5 @@
 """What the ctypes wrappers of the stand-alone device libraries share (``structure`` over libmw_sk.so, ``bondorder`` over
-libmw_boo.so, ``tetrahedral`` over libmw_tet.so, ``angles`` over libmw_adf.so, ``rings`` over libmw_rings.so, ``quench`` over libmw_quench.so, ``dynamics`` over libmw_md.so, ``npt`` over libmw_npt.so, ``timecorr`` over libmw_tcf.so, ``phonons`` over libmw_hess.so): loading, the error check, the one-device life cycle, the plan fields and the checks of the callers' arrays.
+libmw_boo.so, ``tetrahedral`` over libmw_tet.so, ``angles`` over libmw_adf.so, ``rings`` over libmw_rings.so, ``quench`` over libmw_quench.so, ``dynamics`` over libmw_md.so, ``npt`` over libmw_npt.so, ``timecorr`` over libmw_tcf.so, ``phonons`` over libmw_hess.so, ``einstein`` over libmw_ti.so): loading, the error check, the one-device life cycle, the plan fields and the checks of the callers' arrays.
 """
 from __future__ import annotations
 

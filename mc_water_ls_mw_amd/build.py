@@ -4,8 +4,8 @@ include/mw_boo.h), libmw_tet.so (tetrahedral order, d5 and LSI from the sorted n
 libmw_adf.so (the O-O-O angle distribution, include/mw_adf.h), libmw_rings.so (the primitive rings of the bond network,
 include/mw_rings.h), libmw_quench.so (inherent-structure quenches, include/mw_quench.h), libmw_md.so (molecular dynamics,
 include/mw_md.h), libmw_npt.so (molecular dynamics at constant pressure, include/mw_npt.h), libmw_tcf.so (time correlation
-functions of trajectories, include/mw_tcf.h) and libmw_hess.so (the Hessian of the energy and its products with vectors,
-include/mw_hess.h) in-tree with hipcc for gfx950.
+functions of trajectories, include/mw_tcf.h), libmw_hess.so (the Hessian of the energy and its products with vectors,
+include/mw_hess.h) and libmw_ti.so (Einstein-crystal thermodynamic integration, include/mw_ti.h) in-tree with hipcc for gfx950.
 
     python -m mc_water_ls_mw_amd.build [--force]
 
@@ -76,6 +76,10 @@ TCF_DEPS = [TCF_SRC, LIB_HOST, os.path.join(os.path.dirname(PKG), "include", "mw
 HESS_LIB = os.path.join(PKG, "libmw_hess.so")
 HESS_SRC = os.path.join(CSRC, "mw_hess.hip")
 HESS_DEPS = [HESS_SRC, LIB_HOST, LIB_CELLS, LIB_FORCES, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_hess.h")]
+
+TI_LIB = os.path.join(PKG, "libmw_ti.so")
+TI_SRC = os.path.join(CSRC, "mw_ti.hip")
+TI_DEPS = [TI_SRC, LIB_HOST, LIB_CELLS, LIB_FORCES, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_ti.h")]
 
 
 def hipcc_path():
@@ -170,7 +174,13 @@ def build_hess(force=False, verbose=False):
     return _compile(HESS_LIB, [HESS_SRC], HESS_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
 
 
+def build_ti(force=False, verbose=False):
+    """libmw_ti.so: the Einstein-crystal thermodynamic-integration kernels and their C ABI, a translation unit of its own like
+    libmw_md.so, whose step it restates and whose cell and force layers (mw_lib_cells.h, mw_lib_forces.h) it shares."""
+    return _compile(TI_LIB, [TI_SRC], TI_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
+
+
 if __name__ == "__main__":
     force = "--force" in sys.argv
-    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf, build_rings, build_md, build_npt, build_tcf, build_hess, build_quench):
+    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf, build_rings, build_md, build_npt, build_tcf, build_hess, build_ti, build_quench):
         print(builder(force=force, verbose=True))

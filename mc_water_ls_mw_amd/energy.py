@@ -608,6 +608,25 @@ class EnergyModule:
         self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
         return npt.molecular_dynamics_npt(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, nsteps, dt, **kwargs)
 
+    # -- Einstein-crystal thermodynamic integration (libmw_ti.so, include/mw_ti.h; no counterpart in the reference) ------
+    def einstein_md(self, ils, lambdas, springs, nsteps, dt, sites=None, **kwargs):
+        """(pos_out, vel_out, forces [nl, nwater, 3], trace [nl, nsteps // sample_every + 1, 5], blocks [nl, nblocks, 5], status
+        [nl, 2]) -- einstein.einstein_md, which takes the keywords (kT, gamma, pos, vel, mass, seed, streams, step0,
+        sample_every, equil_steps, block_steps) -- of nl = len(``lambdas``) copies of box ``ils`` (from 1), one per lambda of
+        a thermodynamic integration, with the Einstein sites ``sites`` [nwater, 3] (None: the positions the DEVICE holds, which
+        take one host hop; for a free energy pass the box's inherent structure) and this module's hmatrix.  The engine's own
+        positions stay as they are."""
+        from . import einstein
+        self._ils(ils)
+        lambdas = np.atleast_1d(np.asarray(lambdas, dtype=np.float64))
+        if sites is None:
+            sites = np.zeros((1, self.nwater, 3))
+            self._chk(self.L.mw_download_positions_range(ils, 1, _d(sites)))
+        sites = np.asarray(sites, dtype=np.float64).reshape(1, self.nwater, 3)
+        nl = lambdas.size
+        cells = np.repeat(np.asarray(self.hmatrix[ils - 1:ils], dtype=np.float64), nl, axis=0)
+        return einstein.einstein_md(cells, np.repeat(sites, nl, axis=0), lambdas, springs, nsteps, dt, **kwargs)
+
     # -- time correlation functions (libmw_md.so records, libmw_tcf.so correlates; include/mw_tcf.h) ---------------------
     def time_correlations(self, first_ils=1, count=None, nframes=2, steps_per_frame=1, dt=1.0, nlags=None, origin_every=1, q=None, edges=None,
                           hist_lags=(), remove_com=False, with_vacf=True, **md_keywords):

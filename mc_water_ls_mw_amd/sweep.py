@@ -447,6 +447,51 @@ class WalkerFarm:
         f_vib = f_vib.reshape(shape)
         return e_min, f_vib, negative.reshape(shape), iters[:, :, 1].astype(bool), (e_min + f_vib).mean(axis=0)
 
+    def einstein_free_energies(self, kT, nodes=12, spring=None, nsteps=20000, equil_steps=2000, block_steps=1000, dt=None, gamma=None, seed=0,
+                               ftol=1e-10, max_iter=10000, first_global_walker=0):
+        """(F [nwalkers, nlat], err [nwalkers, nlat], f_ti [nlat]): the classical free energy of every lattice of every walker
+        at ``kT`` (Hartree) by Frenkel-Ladd thermodynamic integration to an Einstein crystal (include/mw_ti.h), anharmonic
+        where :meth:`harmonic_free_energies` is not.  The Einstein sites are the inherent structures
+        (:meth:`inherent_structures`); every (walker, lattice, node) of an ``nodes``-point Gauss-Legendre rule in lambda is one
+        box of one call -- its noise stream its flat index, counted from ``first_global_walker`` * nlat * nodes --, run for
+        ``nsteps`` Langevin steps of ``dt`` (5 fs) with ``gamma`` (1 / 100 fs) from its sites, the first ``equil_steps``
+        left out and the rest averaged on the device in blocks of ``block_steps``.  ``spring`` (Hartree / bohr^2, one for all
+        boxes so that the centre of mass cancels between lattices; None: einstein.spring_from_msd of the mean squared
+        displacement of ``equil_steps`` steps at lambda = 0, its second half, averaged over all boxes).  F = einstein.frenkel_ladd
+        without the centre of mass -- it holds the energy of the minimum and stands beside e_min + f_vib of
+        :meth:`harmonic_free_energies` --, err its standard error from the blocks, f_ti the mean of F over the walkers of each
+        lattice: f_ti[1] - f_ti[0] is the estimate to hold beside the lattice-switch free-energy difference.  The walkers'
+        own configurations are left alone."""
+        from . import dynamics, einstein
+        dt = 5.0 * dynamics.FS if dt is None else float(dt)
+        gamma = 1.0 / (100.0 * dynamics.FS) if gamma is None else float(gamma)
+        if not gamma > 0.0:
+            raise ValueError("einstein_free_energies: gamma must be > 0 (the averages are canonical)")
+        nodes = int(nodes)
+        if einstein.nblocks_of(nsteps, equil_steps, block_steps) < 2:
+            raise ValueError("einstein_free_energies: (nsteps - equil_steps) // block_steps must be at least 2 for an error from the blocks")
+        sites, _, _ = self.inherent_structures(ftol, max_iter)
+        n, nb = self.em.nwater, self.em.num_lattices
+        sites = sites.reshape(nb, n, 3)
+        cells = np.asarray(self.em.hmatrix, dtype=np.float64)
+        first = int(first_global_walker) * self.nlat
+        if spring is None:
+            half = max(int(equil_steps) // 2, 1)
+            _, _, _, _, blk, _ = einstein.einstein_md(cells, sites, 0.0, 1.0, 2 * half, dt, kT, gamma, seed=seed, equil_steps=half, block_steps=half,
+                                                      streams=np.uint64(first) + np.arange(nb, dtype=np.uint64))
+            spring = einstein.spring_from_msd(float((blk[:, 0, 2] - blk[:, 0, 4]).mean()), kT)
+        lam, w = einstein.gauss_legendre(nodes)
+        streams = np.uint64(first * nodes) + np.arange(nb * nodes, dtype=np.uint64)
+        _, _, _, _, blocks, _ = einstein.einstein_md(np.repeat(cells, nodes, axis=0), np.repeat(sites, nodes, axis=0), np.tile(lam, nb), float(spring),
+                                                     nsteps, dt, kT, gamma, seed=seed, streams=streams, sample_every=max(int(nsteps), 1),
+                                                     equil_steps=equil_steps, block_steps=block_steps)
+        y = einstein.integrand(blocks, float(spring), n).reshape(nb, nodes, -1)
+        f_e = einstein.einstein_free_energy(n, float(spring), dynamics.MASS_WATER, kT)
+        res = np.array([einstein.frenkel_ladd(lam, w, y[b], f_e) for b in range(nb)])
+        shape = (self.nwalkers, self.nlat)
+        F, err = res[:, 0].reshape(shape), res[:, 1].reshape(shape)
+        return F, err, F.mean(axis=0)
+
     def molecular_dynamics(self, nsteps, dt, first_global_walker=0, **kwargs):
         """(pos_out, vel_out [nwalkers, nlat, nwater, 3], trace [nwalkers, nlat, nsteps // sample_every + 1, 4], status
         [nwalkers, nlat, 2]): ``nsteps`` BAOAB steps of ``dt`` (include/mw_md.h) from the configuration of every lattice of
