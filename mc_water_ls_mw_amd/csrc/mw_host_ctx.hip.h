@@ -185,6 +185,7 @@ struct Ctx {
     bool move_sort = true;             // MW_MOVE_SORT != 0 at mw_moves_upload: the moment path sorts an item's requests by in-range neighbours
     bool move_masks = true;            // MW_MOVE_MASKS != 0 at mw_moves_upload: the sorted moment path rebuilds its queues from the count pass's row-slot masks
     bool move_gate = true;             // MW_MOVE_GATE != 0 at mw_moves_upload: the 0.99 rule's pair pass tests angles only behind the triangle-area gate
+    bool move_pairs32 = true;          // MW_MOVE_PAIRS32 != 0 at mw_moves_upload: a walking group runs the f32 pair gate from its registers in front of that pass
     bool move_counts_eager = false;   // MW_MOVE_COUNTS=eager at mw_init: the launch itself counts, as it used to
     int move_moments = -1;             // MW_MOVE_MOMENTS at mw_init: -1 unset (the request-count rule), 0 scanning path, 1 moment path where admitted
     int mchunk = 16;                 // requests per work item of the uploaded batch

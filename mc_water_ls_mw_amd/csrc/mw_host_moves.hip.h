@@ -69,8 +69,10 @@ int mw_moves_upload(int n, const int* ils, const int* imol, const double* trial_
     g.mlds = lds_fits_move(g.N, g.ivcap) && ((long long)n * 2048 >= (long long)used_boxes * 24 * g.N);
     // Requests per work item.  Inside an item the wavefronts draw requests dynamically, so large items waste little
     // at their end and stage the box once for more work; but there must be enough items to fill the chip:
-    // aim at >= 2 items per CU, between 256 and the LDS capacity kMoveChunk (measured on 512 x 2048 requests: items of
-    // 256 / 512 / 1024 / 2048 requests take 1.375 / 1.316 / 1.291 / 1.286 ms; MW_MOVE_CHUNK overrides).
+    // aim at >= 2 items per CU, between 256 and the LDS capacity kMoveChunk (measured on 512 x 2048 requests with the sorted,
+    // XCD-ordered moment path, profiles/r12_summary.md: items of 512 / 1024 / 2048 requests give a step of 0.504 / 0.492 / 0.488 ms,
+    // medians of five alternating runs -- a smaller item sorts into shorter groups and ends on a shorter tail, and still loses to
+    // staging the box once more; MW_MOVE_CHUNK overrides).
     int chunk = 16;
     if (g.mlds) {
         const long long want = (long long)n / (2LL * std::max(1, g.cu));
@@ -82,6 +84,7 @@ int mw_moves_upload(int n, const int* ils, const int* imol, const double* trial_
     { const char* ms = std::getenv("MW_MOVE_SORT"); g.move_sort = !(ms && ms[0] == '0'); }   // (the moment path: mode bit 5 of k_move_energy)
     { const char* mk = std::getenv("MW_MOVE_MASKS"); g.move_masks = !(mk && mk[0] == '0'); }   // (and its bit 6)
     { const char* mg = std::getenv("MW_MOVE_GATE"); g.move_gate = !(mg && mg[0] == '0'); }     // (and its bit 7)
+    { const char* mp = std::getenv("MW_MOVE_PAIRS32"); g.move_pairs32 = !(mp && mp[0] == '0'); }   // (and its bit 8)
     std::vector<int4> work;
     for (int b = 0; b < g.nbox; ++b) {
         const int s0 = start[b], cntb = start[(size_t)b + 1] - s0;
@@ -148,7 +151,7 @@ static int launch_moves(int mode)
         if (!fresh && launch_model_energy(g.m_boxlo + 1, g.m_boxhi - g.m_boxlo + 1, true, false)) return 1;
         // the counts of the requests this kernel serves: made on demand (mw_moves_counts), by a pass of the same kernel with mode bits
         // 3 "count" and 4 "no energy output"; MW_MOVE_COUNTS=eager: by this launch, as before
-        launch(mw::k_move_energy<true, mw::kLayoutSoA, false, true>, g.d_mom, g.d_mtot, (g.move_counts_eager ? 8 : 0) | (g.move_sort ? 32 : 0) | (g.move_masks ? 64 : 0) | (g.move_gate ? 128 : 0));
+        launch(mw::k_move_energy<true, mw::kLayoutSoA, false, true>, g.d_mom, g.d_mtot, (g.move_counts_eager ? 8 : 0) | (g.move_sort ? 32 : 0) | (g.move_masks ? 64 : 0) | (g.move_gate ? 128 : 0) | (g.move_pairs32 ? 256 : 0));
         if (g.move_counts_eager) g.mtot_n = g.mwork_n;
     } else if (g.mlds && g.m_noself) launch(mw::k_move_energy<true, mw::kLayoutSoA, false>, nullptr, nullptr);
     else if (g.mlds)                 launch(mw::k_move_energy<true>, nullptr, nullptr);
@@ -213,7 +216,7 @@ int mw_moves_counts(long long out[4])
     if (g.mcnt_state == Ctx::kCountsPending) {
         // the launch's moment-path kernel once more, on the same work items, moments and positions: it counts what it serves (d_mtot,
         // zeros in d_mcnt), writes no energy and appends nothing to the declined list -- whose requests k_move_fallback counted at the launch
-        launch_move_kernel(mw::k_move_energy<true, mw::kLayoutSoA, false, true>, move_lds_bytes(g.N, g.ivcap, g.mchunk), g.mmode | 8 | 16 | (g.move_sort ? 32 : 0) | (g.move_masks ? 64 : 0) | (g.move_gate ? 128 : 0), g.d_mom, g.d_mtot);
+        launch_move_kernel(mw::k_move_energy<true, mw::kLayoutSoA, false, true>, move_lds_bytes(g.N, g.ivcap, g.mchunk), g.mmode | 8 | 16 | (g.move_sort ? 32 : 0) | (g.move_masks ? 64 : 0) | (g.move_gate ? 128 : 0) | (g.move_pairs32 ? 256 : 0), g.d_mom, g.d_mtot);
         HIPCHK(hipGetLastError());
         g.mtot_n = g.mwork_n;
         g.mcnt_state = Ctx::kCountsThere;

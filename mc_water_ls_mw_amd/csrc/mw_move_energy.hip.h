@@ -28,7 +28,9 @@ namespace mw {
 //   their number of in-range neighbours before evaluating them (below; MW_MOVE_SORT=0 clears it), bit 6: the pass that counts for
 //   the sort keeps every request's row-slot mask, and a group rebuilds its queues from the masks instead of scanning the rows again
 //   (THE MASK WALK, mw_move_lanes.hip.h; only where bit 5 sorts; MW_MOVE_MASKS=0 clears it), bit 7: the 0.99 rule's pair pass enters
-//   its angle block only for pairs that pass THE GATE (mw_move_lanes.hip.h; MW_MOVE_GATE=0 clears it: every pair with |ab| < cutoff)
+//   its angle block only for pairs that pass THE GATE (mw_move_lanes.hip.h; MW_MOVE_GATE=0 clears it: every pair with |ab| < cutoff),
+//   bit 8: a group that walks the masks runs THE F32 PAIR GATE from its registers first, and the pair pass serves only the queue rows
+//   that names (mw_move_lanes.hip.h; only with bit 7; MW_MOVE_PAIRS32=0 clears it)
 constexpr int kMoveChunk = 2048;   // requests per work item when the box is staged in LDS
 
 // MOMPATH keeps an item's requests in LDS as 32-bit KEYS: molecule | request index in the item << 13 | nq << 24, nq = the entries
@@ -318,7 +320,7 @@ void k_move_energy(const double* __restrict__ pos, const double* __restrict__ iv
             unsigned int ci = 0u, cs = 0u;
             const bool served = move_energy_mom_lanes(getpos, getiv, nnof, LM + (size_t)i * kRow, MOM, wq, qn, i, n_i,
                                                       walk, valid ? (int)(k >> kKeyNqShift) : 0, e8,
-                                                      px, py, pz, lane, count, (mode & 128) != 0, en, ci, cs);
+                                                      px, py, pz, lane, count, (mode & 128) != 0, (mode & 256) != 0, en, ci, cs);
             // (the next group's loads leave HERE, behind the evaluation and ahead of the result stores: issued at the loop's top they
             //  are up to seventeen registers held across the evaluation, which has none to spare -- and a group starts on memory once
             //  per 32 requests, with three other wavefronts of the SIMD to fill the wait)

@@ -52,6 +52,7 @@ __device__ __forceinline__ int pair_swap_i32(int v) { return __builtin_amdgcn_up
 __device__ __forceinline__ int pair_even_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, 0xa0, 0xf, 0xf, true); }   // quad_perm:[0,0,2,2]
 __device__ __forceinline__ double pair_even_f64(double v) { return dpp_mov_f64<0xa0, 0xf>(v); }
 __device__ __forceinline__ double pair_swap_f64(double v) { return dpp_mov_f64<0xb1, 0xf>(v); }
+__device__ __forceinline__ double pair_odd_f64(double v) { return dpp_mov_f64<0xf5, 0xf>(v); }                            // quad_perm:[1,1,3,3]
 
 // r_j + ivect (molint.F90:269) of a row entry: ONE spelling for every in-range decision of the lane-pair routines
 template <typename PosFn, typename IvFn>
@@ -167,19 +168,115 @@ __device__ __forceinline__ void lanes_park(uint32_t* __restrict__ wq, int r, int
     }
 }
 
+// THE F32 PAIR GATE (mode bit 8 of k_move_energy; MW_MOVE_PAIRS32=0 clears it).  The pair loop of move_energy_mom_lanes gathers
+// every entry of a queue from LDS once per pair it belongs to, in FP64, to decide a factor-two superset test.  A group that WALKS
+// THE MASKS has its entries in registers already -- lane `side` holds entries side, side + 2, ... of its request in `ent` -- so it
+// first runs the gate from registers, in f32, and the FP64 loop afterwards serves only the queue rows `a` for which some lane's
+// f32 gate fired (on thermal ice ~10 pairs per 2048 requests): that loop, its gate and its angle block are unchanged, so `hard`
+// is what it was as long as the f32 gate passes every pair the rule drops.
+//   set-up  a lane gathers the image of each of its entries once (lanes_image, FP64), forms a - P and a - P' in FP64 (P the OLD
+//           position in both lanes, P' the trial one) and keeps five f32 words: v = fl(a - P), Qo = fl(|a - P|^2), Qn = fl(|a - P'|^2).
+//           An entry past the queue's end gets v.x = NaN: no pair with it is `near`.
+//   pairs   entry a's five words come from their owner to both lanes of the pair on the DPP network (quad_perm [0,0,2,2] for an even
+//           a, [1,1,3,3] for an odd one), a lane's b are its OWN entries c with 2c + side > a: the pairs of a queue are split by b's
+//           parity, every pair is met once.  A lane index cannot index registers, so the (a, c) triangle is unrolled, with
+//           wave-uniform exits at the group's longest queue (groups are sorted by nq: the exits are tight).
+//   test    S = |v_b - v_a|^2 < rc^2 (1 + 1e-5) and thin(Qo_a, Qo_b, S) or thin(Qn_a, Qn_b, S) -- the two as one packed evaluation.
+// THE BOUND.  A group holding a request moved by more than 16 bohr, or an entry nearer than 0.03 rc to either position, leaves all
+// its rows to the FP64 loop (`wide`).  Otherwise every component of v is below 32 bohr, so a component of v_b - v_a is off by at
+// most d = 2.4e-6 bohr (two roundings at ulp(32)/2, one of the difference), S by 2 sqrt(3) |ab| d + 3 roundings < 8e-5 bohr^2 = 1.2e-6
+// rc^2 where |ab| <= rc -- inside the 1e-5 of `near` -- and t/2 = (Q + R - S)/2 by e <= sqrt(3) (sqrt(Q) + sqrt(R)) d + 2e-7 max(Q, R, S).
+// The left side QR - (t/2)^2 moves by 2 sqrt(QR) e + 2e-7 QR: for a dropped triplet (both arms between 0.03 rc and rc, S <= 4 R) below
+// 1e-4 QR, where the gate keeps 0.0197 max(QR, QS, RS) over the rule -- the same factor of two, to 0.5 % (tests/test_move_pairs32_ref.py
+// holds left <= 0.52 right for dropped triangles in either order of evaluation, fused or not).
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+constexpr double kPairsWide2 = 256.0;                            // bohr^2
+constexpr float kPairsTiny = (float)(0.03 * 0.03 * kRcSq);
+constexpr unsigned long long kEvenLanes = 0x5555555555555555ull;
+
+__device__ __forceinline__ int pair_odd_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, 0xf5, 0xf, 0xf, true); }    // quad_perm:[1,1,3,3]
+__device__ __forceinline__ float pair_even_f32(float v) { return __int_as_float(pair_even_i32(__float_as_int(v))); }
+__device__ __forceinline__ float pair_odd_f32(float v) { return __int_as_float(pair_odd_i32(__float_as_int(v))); }
+
+// Returns the rows a (bit a) of the group's queues that the FP64 pair loop has to serve: wave-uniform.  (px, py, pz) = this lane's
+// position (the old one in the even lane, the trial one in the odd lane); every lane of the wavefront is active.
+template <typename ImageFn>
+__device__ __forceinline__ uint32_t lanes_pairs32(ImageFn image, const uint32_t (&ent)[kLaneWalk], int side, int nq,
+                                                  double px, double py, double pz)
+{
+    const int left = nq - side;                                  // (entry c of this lane is live when 2c < left, as in lanes_park)
+    int nqmax = 0;                                               // the group's longest queue (scalar)
+#pragma unroll
+    for (int c = 0; c < kLaneWalk; ++c) {
+        const unsigned long long m = __ballot(2 * c < left);
+        if (m & kEvenLanes) nqmax = 2 * c + 1;
+        if (m & ~kEvenLanes) nqmax = 2 * c + 2;
+    }
+    if (nqmax < 2) return 0u;
+    const int cmax = (nqmax + 1) >> 1;                           // registers in use
+    const double ox = pair_even_f64(px), oy = pair_even_f64(py), oz = pair_even_f64(pz);          // P
+    const double nx = pair_odd_f64(px), ny = pair_odd_f64(py), nz = pair_odd_f64(pz);             // P'
+    bool wide = dist2(nx - ox, ny - oy, nz - oz) > kPairsWide2;
+    float vx[kLaneWalk], vy[kLaneWalk], vz[kLaneWalk];
+    f32x2 qq[kLaneWalk];                                         // (Qo, Qn)
+#pragma unroll
+    for (int c = 0; c < kLaneWalk; ++c) {
+        if (c >= cmax) continue;                                 // (wave-uniform; no `break`: the loop unrolls)
+        const bool live = 2 * c < left;
+        double qx, qy, qz;
+        image(live ? ent[c] : 0u, qx, qy, qz);
+        const double dx = qx - ox, dy = qy - oy, dz = qz - oz;
+        const double Qo = dist2(dx, dy, dz), Qn = dist2(qx - nx, qy - ny, qz - nz);
+        vx[c] = live ? (float)dx : __builtin_nanf("");
+        vy[c] = (float)dy; vz[c] = (float)dz;
+        qq[c] = f32x2{(float)Qo, (float)Qn};
+        wide = wide || (live && fminf(qq[c].x, qq[c].y) < kPairsTiny);
+    }
+    if (__ballot(wide) != 0ull) return ~0u;
+
+    constexpr float kThin32 = (float)(1.0 - 0.98 * 0.98), kNear32 = (float)(kRcSq * (1.0 + 1e-5));
+    uint32_t rows = 0u;
+#pragma unroll
+    for (int a = 0; a + 1 < kLaneQueue; ++a) {                   // (unrolled: a, and with it the owner's lane and register, are constants)
+        if (a + 1 >= nqmax) continue;
+        const int k = a >> 1;
+        const bool odd = (a & 1) != 0;
+        auto from = [&](float v) { return odd ? pair_odd_f32(v) : pair_even_f32(v); };
+        const float ax = from(vx[k]), ay = from(vy[k]), az = from(vz[k]);
+        const f32x2 Q = {from(qq[k].x), from(qq[k].y)};
+        const f32x2 hQ = 0.5f * Q;
+        bool fire = false;
+#pragma unroll
+        for (int c = (a + 1) >> 1; c < kLaneWalk; ++c) {         // (c = k of an even a: the odd lane's pair (a, a + 1) alone)
+            if (c >= cmax) continue;
+            const float dx = vx[c] - ax, dy = vy[c] - ay, dz = vz[c] - az;
+            const float S = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+            const f32x2 R = qq[c], S2 = {S, S};
+            const f32x2 th = 0.5f * (R - S2) + hQ, QR = Q * R, QS = Q * S2, RS = R * S2;
+            const f32x2 left = QR - th * th;
+            const bool thin = left.x <= kThin32 * fmaxf(fmaxf(QR.x, QS.x), RS.x) || left.y <= kThin32 * fmaxf(fmaxf(QR.y, QS.y), RS.y);
+            const bool mine = 2 * c > a || side != 0;            // 2c + side > a
+            fire = fire || (mine && S < kNear32 && thin);
+        }
+        if (__ballot(fire) != 0ull) rows |= 1u << a;
+    }
+    return rows;
+}
+
 // One group: this lane's request is molecule `i` (row length n_i; 0 = no request in this lane), its row `rowp` = LM + i * kRow, and
 // (px, py, pz) the position this lane evaluates: the old one in the even lane, the trial one in the odd lane.  `wq` = the
 // wavefront's queue words, `qn` = its 32 queue lengths (bytes).  `walk` (wave-uniform): every request of the group comes with the
 // length of its queue, `nq_key` -- at most kLaneQueue, and no molecule lists itself: the count pass has taken those requests out --
 // and `ent` = what lanes_entries loaded for this lane; else `ent[0..3]` = the first four entries of the row, and phase 1 scans it.
 // Returns false when the request is declined (the same answer in both lanes of a pair); else `E` = the local energy at this lane's
-// position and, when `count` (wave-uniform), `ci` / `cs` = its interactions and list slots.  `gate` (wave-uniform): THE GATE above.
+// position and, when `count` (wave-uniform), `ci` / `cs` = its interactions and list slots.  `gate` (wave-uniform): THE GATE above;
+// `pairs32` (wave-uniform): a walking group runs THE F32 PAIR GATE in front of it.
 template <typename PosFn, typename IvFn, typename NnFn>
 __device__ __forceinline__ bool move_energy_mom_lanes(PosFn getpos, IvFn getiv, NnFn nnof, const uint32_t* __restrict__ rowp,
                                                       const double* __restrict__ MOM, uint32_t* __restrict__ wq, unsigned char* __restrict__ qn,
                                                       int i, int n_i, bool walk, int nq_key, const uint32_t (&ent)[kLaneWalk],
                                                       double px, double py, double pz,
-                                                      int lane, bool count, bool gate, double& E, unsigned int& ci, unsigned int& cs)
+                                                      int lane, bool count, bool gate, bool pairs32, double& E, unsigned int& ci, unsigned int& cs)
 {
     const int r = lane >> 1, side = lane & 1;
     auto image = [&](uint32_t e, double& qx, double& qy, double& qz) { lanes_image(getpos, getiv, e, qx, qy, qz); };
@@ -204,13 +301,16 @@ __device__ __forceinline__ bool move_energy_mom_lanes(PosFn getpos, IvFn getiv, 
 
     // ---- the 0.99 rule: the queue's pairs, shared between the two lanes --------------------------------------------------------
     bool hard = false;
-    const double tx = pair_swap_f64(px), ty = pair_swap_f64(py), tz = pair_swap_f64(pz);           // P': the partner's position
     constexpr double kThin = 1.0 - 0.98 * 0.98;
     auto thin = [&](double Q, double R, double S) {              // (the header: QR - (t/2)^2 <= kThin max(QR, QS, RS))
         const double th = __builtin_fma(0.5, R - S, 0.5 * Q), QR = Q * R;
         return __builtin_fma(-th, th, QR) <= kThin * fmax(fmax(QR, Q * S), R * S);
     };
-    for (int a = 0; __ballot(a + 1 < nq) != 0ull; ++a) {
+    // (a walking group behind THE F32 PAIR GATE: only the rows that gate names)
+    const uint32_t rows = walk && gate && pairs32 ? lanes_pairs32(image, ent, side, nq, px, py, pz) : ~0u;
+    const double tx = pair_swap_f64(px), ty = pair_swap_f64(py), tz = pair_swap_f64(pz);           // P': the partner's position
+    for (int a = 0; (rows >> a) != 0u && __ballot(a + 1 < nq) != 0ull; ++a) {
+        if (!(rows >> a & 1u)) continue;
         double ax, ay, az;
         image(a + 1 < nq ? wq[a * 32 + r] : 0u, ax, ay, az);
         double Q = 0.0, Qt = 0.0;
