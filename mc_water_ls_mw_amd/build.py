@@ -5,7 +5,8 @@ libmw_adf.so (the O-O-O angle distribution, include/mw_adf.h), libmw_rings.so (t
 include/mw_rings.h), libmw_quench.so (inherent-structure quenches, include/mw_quench.h), libmw_md.so (molecular dynamics,
 include/mw_md.h), libmw_npt.so (molecular dynamics at constant pressure, include/mw_npt.h), libmw_tcf.so (time correlation
 functions of trajectories, include/mw_tcf.h), libmw_hess.so (the Hessian of the energy and its products with vectors,
-include/mw_hess.h) and libmw_ti.so (Einstein-crystal thermodynamic integration, include/mw_ti.h) in-tree with hipcc for gfx950.
+include/mw_hess.h), libmw_ti.so (Einstein-crystal thermodynamic integration, include/mw_ti.h) and libmw_flex.so (molecular
+dynamics at constant pressure with a per-axis cell and the pressure tensor, include/mw_flex.h) in-tree with hipcc for gfx950.
 
     python -m mc_water_ls_mw_amd.build [--force]
 
@@ -80,6 +81,10 @@ HESS_DEPS = [HESS_SRC, LIB_HOST, LIB_CELLS, LIB_FORCES, os.path.join(CSRC, "mw_c
 TI_LIB = os.path.join(PKG, "libmw_ti.so")
 TI_SRC = os.path.join(CSRC, "mw_ti.hip")
 TI_DEPS = [TI_SRC, LIB_HOST, LIB_CELLS, LIB_FORCES, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_ti.h")]
+
+FLEX_LIB = os.path.join(PKG, "libmw_flex.so")
+FLEX_SRC = os.path.join(CSRC, "mw_flex.hip")
+FLEX_DEPS = [FLEX_SRC, LIB_HOST, LIB_CELLS, LIB_FORCES, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_flex.h")]
 
 
 def hipcc_path():
@@ -180,7 +185,14 @@ def build_ti(force=False, verbose=False):
     return _compile(TI_LIB, [TI_SRC], TI_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
 
 
+def build_flex(force=False, verbose=False):
+    """libmw_flex.so: the per-axis constant-pressure molecular-dynamics kernels and their C ABI, a translation unit of its own
+    like libmw_npt.so, whose step it restates and whose cell and force layers (mw_lib_cells.h, mw_lib_forces.h, with the stress)
+    it shares."""
+    return _compile(FLEX_LIB, [FLEX_SRC], FLEX_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
+
+
 if __name__ == "__main__":
     force = "--force" in sys.argv
-    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf, build_rings, build_md, build_npt, build_tcf, build_hess, build_ti, build_quench):
+    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf, build_rings, build_md, build_npt, build_tcf, build_hess, build_ti, build_flex, build_quench):
         print(builder(force=force, verbose=True))

@@ -1,6 +1,7 @@
 // The force layer the inherent-structure quenches and the molecular dynamics (mw_md.hip, mw_npt.hip) share: a molecule's
 // moments and energy (Sums), the derivative of its triplet sum against a centre's moments (triplet_grad), the force one entry
-// puts on it (entry_force) and that entry's share of the scalar virial (entry_virial, used by mw_npt.hip alone), the cell held
+// puts on it (entry_force), that entry's share of the scalar virial (entry_virial, used by mw_npt.hip alone) and of the virial
+// tensor (entry_stress, used by mw_flex.hip alone), the cell held
 // in vector registers (CellRegs / in_vgpr) and the reductions in a fixed order (the DPP trees of a wavefront, block_reduce over
 // the wavefronts of a workgroup).  Device code only, all of it inlined: every library
 // compiles it into its own kernels and exports nothing from here.  Included after `#pragma clang fp contract(off)`, after
@@ -112,6 +113,24 @@ __device__ __forceinline__ void entry_virial(const double (&Mi)[kMom], const dou
     dw = dw + __builtin_fma(dx, ex, __builtin_fma(dy, ey, dz * ez));
 }
 __device__ __forceinline__ double lane_virial(double dw) { return -0.5 * dw; }
+
+// entry_virial, and the entry's share of the virial tensor (mw_flex.hip alone): f and dw get the bits entry_virial gives them;
+// s holds the lane's sums in the order xx, yy, zz, xy, xz, yz, s_aa = fma(d_a, e_a, s_aa) and, symmetrised,
+// s_ab = s_ab + fma(d_a, e_b, d_b e_a).  Every pair is visited from both ends as for W, and an off-diagonal sum counts d_a e_b and
+// d_b e_a both: the lane's share of W_ab is -1/2 s on the diagonal and -1/4 s off it (lane_stress).
+__device__ __forceinline__ void entry_stress(const double (&Mi)[kMom], const double (&Mj)[kMom], double r2, double dx, double dy, double dz,
+                                             double& fx, double& fy, double& fz, double& dw, double (&s)[6])
+{
+    double ex = 0.0, ey = 0.0, ez = 0.0;
+    entry_force(Mi, Mj, r2, dx, dy, dz, ex, ey, ez);
+    fx = fx + ex; fy = fy + ey; fz = fz + ez;
+    dw = dw + __builtin_fma(dx, ex, __builtin_fma(dy, ey, dz * ez));
+    s[0] = __builtin_fma(dx, ex, s[0]); s[1] = __builtin_fma(dy, ey, s[1]); s[2] = __builtin_fma(dz, ez, s[2]);
+    s[3] = s[3] + __builtin_fma(dx, ey, dy * ex);
+    s[4] = s[4] + __builtin_fma(dx, ez, dz * ex);
+    s[5] = s[5] + __builtin_fma(dy, ez, dz * ey);
+}
+__device__ __forceinline__ double lane_stress(double s, int k) { return k < 3 ? -0.5 * s : -0.25 * s; }
 
 // The cell's nine doubles held in vector registers.  Left to itself the compiler keeps them in 18 scalar registers next to the
 // scalar constants of pair_terms' polynomial, and the walks of the force pass then run out of scalar registers and spill.

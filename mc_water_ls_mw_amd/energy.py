@@ -608,6 +608,17 @@ class EnergyModule:
         self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
         return npt.molecular_dynamics_npt(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, nsteps, dt, **kwargs)
 
+    def molecular_dynamics_flex(self, first_ils=1, count=None, nsteps=0, dt=1.0, **kwargs):
+        """The seven results of :meth:`molecular_dynamics_npt` with a per-axis cell and a trace of 15 columns --
+        flexcell.molecular_dynamics_flex, which takes the keywords of the NPT call and ``coupling`` and ``axis`` -- from the
+        positions the DEVICE holds and this module's hmatrix; the engine's own positions and cells stay as they are."""
+        from . import flexcell
+        count = self.num_lattices - first_ils + 1 if count is None else count
+        self._ils(first_ils), self._ils(first_ils + count - 1)
+        pos = np.zeros((count, self.nwater, 3))
+        self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
+        return flexcell.molecular_dynamics_flex(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, nsteps, dt, **kwargs)
+
     # -- Einstein-crystal thermodynamic integration (libmw_ti.so, include/mw_ti.h; no counterpart in the reference) ------
     def einstein_md(self, ils, lambdas, springs, nsteps, dt, sites=None, **kwargs):
         """(pos_out, vel_out, forces [nl, nwater, 3], trace [nl, nsteps // sample_every + 1, 5], blocks [nl, nblocks, 5], status

@@ -528,6 +528,23 @@ class WalkerFarm:
         return (pos_out.reshape(*shape, self.em.nwater, 3), vel_out.reshape(*shape, self.em.nwater, 3), cells_out.reshape(*shape, 3, 3),
                 trace.reshape(*shape, -1, 6), status.reshape(*shape, 2))
 
+    def molecular_dynamics_flex(self, nsteps, dt, first_global_walker=0, **kwargs):
+        """(pos_out, vel_out [nwalkers, nlat, nwater, 3], cells_out [nwalkers, nlat, 3, 3], trace [nwalkers, nlat, nsteps //
+        sample_every + 1, 15], status [nwalkers, nlat, 2]): :meth:`molecular_dynamics_npt` with a cell whose Cartesian axes move
+        on their own and the pressure tensor in the trace (include/mw_flex.h), with the keywords of
+        flexcell.molecular_dynamics_flex (``pressure`` defaults to the farm's own, then coupling, axis and those of the NPT call)
+        and the same noise streams.  The walkers' own configurations and cells are left alone."""
+        if "streams" in kwargs:
+            raise ValueError("the farm names the noise streams itself: (first_global_walker + walker) * nlat + lattice")
+        self.sync_cells()
+        nb = self.em.num_lattices
+        streams = np.uint64(int(first_global_walker) * self.nlat) + np.arange(nb, dtype=np.uint64)
+        kwargs.setdefault("pressure", self.pressure)
+        pos_out, vel_out, _, cells_out, _, trace, status = self.em.molecular_dynamics_flex(1, nb, nsteps, dt, streams=streams, **kwargs)
+        shape = (self.nwalkers, self.nlat)
+        return (pos_out.reshape(*shape, self.em.nwater, 3), vel_out.reshape(*shape, self.em.nwater, 3), cells_out.reshape(*shape, 3, 3),
+                trace.reshape(*shape, -1, 15), status.reshape(*shape, 2))
+
     def time_correlations(self, nframes, steps_per_frame, dt, first_global_walker=0, **kwargs):
         """(msd, mqd, vacf [nlat, nlags], fs [nlat, nlags, nq], hist [nlat, nh, nedges + 1], status [nwalkers, nlat, 2]): the time
         correlation functions (include/mw_tcf.h) of a recorded molecular-dynamics run of ``nframes`` frames, ``steps_per_frame``
