@@ -1,5 +1,7 @@
-// The cell layer libmw_boo.so, libmw_tet.so, libmw_adf.so and libmw_rings.so share: how a molecule's neighbour entries are
-// found.  General geometry (nwater > 64): a fractional cell grid, a counting sort into it (k_cells_bin, k_cells_scan,
+// The cell layer ten libraries share: how a molecule's neighbour entries are found.  The four analysis libraries include it
+// themselves (bond order, tetrahedral order, angle distribution, rings); the six force libraries reach it through
+// mw_lib_forces.h (quench, dynamics at constant volume and at constant pressure with a scalar and a per-axis cell, the Hessian,
+// thermodynamic integration).  General geometry (nwater > 64): a fractional cell grid, a counting sort into it (k_cells_bin, k_cells_scan,
 // k_cells_place, k_cells_rank) and walk_cells, one lane per molecule in sorted order over the 27 neighbouring cells.  Small
 // geometry (nwater <= 64): walk_small, one wavefront per box over the eight image combinations of every j.  Included after
 // `#pragma clang fp contract(off)` and after mw_lib_host.h.  Like that header it exports nothing: the kernels live in the

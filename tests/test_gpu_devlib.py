@@ -1,6 +1,7 @@
 """GPU: what libmw_sk.so and libmw_boo.so have in common through csrc/mw_lib_host.h and _devlib.py -- a call leaves the
-caller's device current, tensors of another device than the library's are refused in Python, and a library that was
-finalised and initialised again gives the same bits and has forgotten its last call."""
+caller's device current, tensors of another device than the library's are refused in Python -- and what every library on that
+header's Runtime has, libmw_sk.so and the ten on the cell layer: one that was finalised and initialised again gives the same
+bits and has forgotten its last call."""
 import numpy as np
 import pytest
 
@@ -13,11 +14,11 @@ NVEC = np.array([[1, 0, 0], [0, 1, 1], [-1, 2, 0]], dtype=np.int32)
 
 @pytest.fixture(scope="module", autouse=True)
 def _library_lifetime():
-    """Later files find both libraries as this one found them: not initialised."""
+    """Later files find the libraries as this one found them: not initialised."""
     yield
-    from mc_water_ls_mw_amd import bondorder, structure
-    structure.sk_finalize()
-    bondorder.boo_finalize()
+    import importlib
+    for which, module in LIBRARIES.items():
+        getattr(importlib.import_module("mc_water_ls_mw_amd." + module), f"{which}_finalize")()
 
 
 def _sk_call():
@@ -33,6 +34,36 @@ def _boo_call():
     from mc_water_ls_mw_amd.bondorder import bond_order
     z = load_golden("ih8_small")
     return bond_order(z["h"], z["xyz"])
+
+
+def _ice_call(which):
+    """The smallest call of an analysis library, host pointers: the golden eight-molecule box at 3.5 Angstrom."""
+    from mc_water_ls_mw_amd.angles import angle_counts
+    from mc_water_ls_mw_amd.rings import ring_statistics
+    from mc_water_ls_mw_amd.tetrahedral import tetrahedral_order
+    z = load_golden("ih8_small")
+    return {"tet": lambda: tetrahedral_order(z["h"], z["xyz"], 3.5, 3.5), "adf": lambda: angle_counts(z["h"], z["xyz"], 3.5),
+            "rings": lambda: ring_statistics(z["h"], z["xyz"], 3.5)}[which]()
+
+
+def _gas_call(which):
+    """A single point of a force library, host pointers: the golden dense gas of 20 molecules."""
+    from mc_water_ls_mw_amd.dynamics import molecular_dynamics
+    from mc_water_ls_mw_amd.einstein import einstein_md
+    from mc_water_ls_mw_amd.flexcell import molecular_dynamics_flex
+    from mc_water_ls_mw_amd.npt import molecular_dynamics_npt
+    from mc_water_ls_mw_amd.phonons import hessian
+    from mc_water_ls_mw_amd.quench import inherent_structures
+    z = load_golden("gas20")
+    h, xyz = z["h"], z["xyz"]
+    return {"quench": lambda: inherent_structures(h, xyz, 1e-10, 0), "md": lambda: molecular_dynamics(h, xyz, 0, 200.0),
+            "npt": lambda: molecular_dynamics_npt(h, xyz, 0, 200.0, baro_every=0), "flex": lambda: molecular_dynamics_flex(h, xyz, 0, 200.0, baro_every=0),
+            "hess": lambda: hessian(h, xyz), "ti": lambda: einstein_md(h, xyz + 0.05, 0.3, 0.02, 0, 200.0, pos=xyz)}[which]()
+
+
+#: the library's name in its symbols -> its module
+LIBRARIES = {"sk": "structure", "boo": "bondorder", "tet": "tetrahedral", "adf": "angles", "rings": "rings", "quench": "quench", "md": "dynamics",
+             "npt": "npt", "flex": "flexcell", "hess": "phonons", "ti": "einstein"}
 
 
 def _same(a, b):
@@ -85,10 +116,11 @@ def test_tensors_of_another_device_are_refused():
     assert (sk_last(), boo_last()) == last
 
 
-@pytest.mark.parametrize("which", ["sk", "boo"])
+@pytest.mark.parametrize("which", list(LIBRARIES))
 def test_finalize_then_init_again(which):
-    from mc_water_ls_mw_amd import bondorder, structure
-    mod, call = (structure, _sk_call) if which == "sk" else (bondorder, _boo_call)
+    import importlib
+    mod = importlib.import_module("mc_water_ls_mw_amd." + LIBRARIES[which])
+    call = {"sk": _sk_call, "boo": _boo_call}.get(which) or (lambda: (_ice_call if which in ("tet", "adf", "rings") else _gas_call)(which))
     init, finalize, last = (getattr(mod, f"{which}_{name}") for name in ("init", "finalize", "last"))
     L = getattr(mod, f"load_{which}_library")()
     is_live = getattr(L, f"mw_{which}_is_initialised")
