@@ -5,8 +5,9 @@ libmw_adf.so (the O-O-O angle distribution, include/mw_adf.h), libmw_rings.so (t
 include/mw_rings.h), libmw_quench.so (inherent-structure quenches, include/mw_quench.h), libmw_md.so (molecular dynamics,
 include/mw_md.h), libmw_npt.so (molecular dynamics at constant pressure, include/mw_npt.h), libmw_tcf.so (time correlation
 functions of trajectories, include/mw_tcf.h), libmw_hess.so (the Hessian of the energy and its products with vectors,
-include/mw_hess.h), libmw_ti.so (Einstein-crystal thermodynamic integration, include/mw_ti.h) and libmw_flex.so (molecular
-dynamics at constant pressure with a per-axis cell and the pressure tensor, include/mw_flex.h) in-tree with hipcc for gfx950.
+include/mw_hess.h), libmw_ti.so (Einstein-crystal thermodynamic integration, include/mw_ti.h), libmw_flex.so (molecular
+dynamics at constant pressure with a per-axis cell and the pressure tensor, include/mw_flex.h) and libmw_pin.so (interface
+pinning: that step with a bias on a collective density mode, include/mw_pin.h) in-tree with hipcc for gfx950.
 
     python -m mc_water_ls_mw_amd.build [--force]
 
@@ -85,6 +86,10 @@ TI_DEPS = [TI_SRC, LIB_HOST, LIB_CELLS, LIB_FORCES, os.path.join(CSRC, "mw_commo
 FLEX_LIB = os.path.join(PKG, "libmw_flex.so")
 FLEX_SRC = os.path.join(CSRC, "mw_flex.hip")
 FLEX_DEPS = [FLEX_SRC, LIB_HOST, LIB_CELLS, LIB_FORCES, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_flex.h")]
+
+PIN_LIB = os.path.join(PKG, "libmw_pin.so")
+PIN_SRC = os.path.join(CSRC, "mw_pin.hip")
+PIN_DEPS = [PIN_SRC, LIB_HOST, LIB_CELLS, LIB_FORCES, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_pin.h")]
 
 
 def hipcc_path():
@@ -192,7 +197,13 @@ def build_flex(force=False, verbose=False):
     return _compile(FLEX_LIB, [FLEX_SRC], FLEX_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
 
 
+def build_pin(force=False, verbose=False):
+    """libmw_pin.so: the interface-pinning kernels and their C ABI, a translation unit of its own like libmw_flex.so, whose step
+    it restates with the force of a harmonic bias on one collective density mode added."""
+    return _compile(PIN_LIB, [PIN_SRC], PIN_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
+
+
 if __name__ == "__main__":
     force = "--force" in sys.argv
-    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf, build_rings, build_md, build_npt, build_tcf, build_hess, build_ti, build_flex, build_quench):
+    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf, build_rings, build_md, build_npt, build_tcf, build_hess, build_ti, build_flex, build_pin, build_quench):
         print(builder(force=force, verbose=True))

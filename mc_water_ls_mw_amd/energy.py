@@ -619,6 +619,19 @@ class EnergyModule:
         self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
         return flexcell.molecular_dynamics_flex(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, nsteps, dt, **kwargs)
 
+    # -- interface pinning (libmw_pin.so, include/mw_pin.h; no counterpart in the reference) ------------------------------
+    def interface_pinning(self, nvec, kappa, anchor, first_ils=1, count=None, nsteps=0, dt=1.0, **kwargs):
+        """The eight results of pinning.interface_pinning -- the seven of :meth:`molecular_dynamics_flex` with a trace of 17
+        columns, and the block averages before the status -- under the bias 1/2 ``kappa`` (Q - ``anchor``)^2 on the mode ``nvec``
+        of every box, from the positions the DEVICE holds and this module's hmatrix; the other keywords are those of
+        pinning.interface_pinning.  The engine's own positions and cells stay as they are."""
+        from . import pinning
+        count = self.num_lattices - first_ils + 1 if count is None else count
+        self._ils(first_ils), self._ils(first_ils + count - 1)
+        pos = np.zeros((count, self.nwater, 3))
+        self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
+        return pinning.interface_pinning(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, nvec, kappa, anchor, nsteps, dt, **kwargs)
+
     # -- Einstein-crystal thermodynamic integration (libmw_ti.so, include/mw_ti.h; no counterpart in the reference) ------
     def einstein_md(self, ils, lambdas, springs, nsteps, dt, sites=None, **kwargs):
         """(pos_out, vel_out, forces [nl, nwater, 3], trace [nl, nsteps // sample_every + 1, 5], blocks [nl, nblocks, 5], status

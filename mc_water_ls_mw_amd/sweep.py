@@ -545,6 +545,24 @@ class WalkerFarm:
         return (pos_out.reshape(*shape, self.em.nwater, 3), vel_out.reshape(*shape, self.em.nwater, 3), cells_out.reshape(*shape, 3, 3),
                 trace.reshape(*shape, -1, 15), status.reshape(*shape, 2))
 
+    def interface_pinning(self, nvec, kappa, anchor, nsteps, dt, first_global_walker=0, **kwargs):
+        """(pos_out, vel_out [nwalkers, nlat, nwater, 3], cells_out [nwalkers, nlat, 3, 3], trace [nwalkers, nlat, nsteps //
+        sample_every + 1, 17], blocks [nwalkers, nlat, nblocks, 4], status [nwalkers, nlat, 2]): :meth:`molecular_dynamics_flex`
+        under the bias 1/2 ``kappa`` (Q - ``anchor``)^2 on the mode ``nvec`` (include/mw_pin.h; one value for every box, or one
+        per box in the order walker, lattice), with the keywords of pinning.interface_pinning (``pressure`` defaults to the
+        farm's own) and the same noise streams.  The walkers' own configurations and cells are left alone."""
+        if "streams" in kwargs:
+            raise ValueError("the farm names the noise streams itself: (first_global_walker + walker) * nlat + lattice")
+        self.sync_cells()
+        nb = self.em.num_lattices
+        streams = np.uint64(int(first_global_walker) * self.nlat) + np.arange(nb, dtype=np.uint64)
+        kwargs.setdefault("pressure", self.pressure)
+        pos_out, vel_out, _, cells_out, _, trace, blocks, status = self.em.interface_pinning(nvec, kappa, anchor, 1, nb, nsteps, dt, streams=streams,
+                                                                                             **kwargs)
+        shape = (self.nwalkers, self.nlat)
+        return (pos_out.reshape(*shape, self.em.nwater, 3), vel_out.reshape(*shape, self.em.nwater, 3), cells_out.reshape(*shape, 3, 3),
+                trace.reshape(*shape, -1, 17), blocks.reshape(*shape, blocks.shape[1], 4), status.reshape(*shape, 2))
+
     def time_correlations(self, nframes, steps_per_frame, dt, first_global_walker=0, **kwargs):
         """(msd, mqd, vacf [nlat, nlags], fs [nlat, nlags, nq], hist [nlat, nh, nedges + 1], status [nwalkers, nlat, 2]): the time
         correlation functions (include/mw_tcf.h) of a recorded molecular-dynamics run of ``nframes`` frames, ``steps_per_frame``
