@@ -1,6 +1,7 @@
 """GPU: pair-distance histograms (mw_rdf*, EnergyModule.rdf_counts / rdf_counts_batch / rdf_launch / rdf, WalkerFarm.rdf)
 against the numpy reference of tests/rdf_ref.py, under its comparison rule: cumulative counts may differ at a bin edge by
-no more than the pairs the reference finds within 1e-9 bohr of that edge, and at most one edge of an input has any."""
+no more than the pairs the reference finds within 1e-9 bohr of that edge, and at most one edge of an input has any.
+Odd N, an odd number of tiles, ragged last tiles and 1 / 7 / 4096 bins on both kernels: tests/test_gpu_derived_shapes.py."""
 import ctypes
 
 import numpy as np
