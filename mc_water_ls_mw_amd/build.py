@@ -6,8 +6,9 @@ include/mw_rings.h), libmw_quench.so (inherent-structure quenches, include/mw_qu
 include/mw_md.h), libmw_npt.so (molecular dynamics at constant pressure, include/mw_npt.h), libmw_tcf.so (time correlation
 functions of trajectories, include/mw_tcf.h), libmw_hess.so (the Hessian of the energy and its products with vectors,
 include/mw_hess.h), libmw_ti.so (Einstein-crystal thermodynamic integration, include/mw_ti.h), libmw_flex.so (molecular
-dynamics at constant pressure with a per-axis cell and the pressure tensor, include/mw_flex.h) and libmw_pin.so (interface
-pinning: that step with a bias on a collective density mode, include/mw_pin.h) in-tree with hipcc for gfx950.
+dynamics at constant pressure with a per-axis cell and the pressure tensor, include/mw_flex.h), libmw_pin.so (interface
+pinning: that step with a bias on a collective density mode, include/mw_pin.h) and libmw_nuc.so (that step with the size of the
+largest solid-like cluster watched and stopping rules on the device, include/mw_nuc.h) in-tree with hipcc for gfx950.
 
     python -m mc_water_ls_mw_amd.build [--force]
 
@@ -43,7 +44,8 @@ SK_DEPS = [SK_SRC, LIB_HOST, os.path.join(CSRC, "mw_common.hip.h"), os.path.join
 
 BOO_LIB = os.path.join(PKG, "libmw_boo.so")
 BOO_SRC = os.path.join(CSRC, "mw_boo.hip")
-BOO_DEPS = [BOO_SRC, LIB_HOST, LIB_CELLS, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_boo.h")]
+LIB_HARMONICS = os.path.join(CSRC, "mw_lib_harmonics.h")   # the real harmonics of l = 4 and 6 libmw_boo.so and libmw_nuc.so share
+BOO_DEPS = [BOO_SRC, LIB_HOST, LIB_CELLS, LIB_HARMONICS, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_boo.h")]
 
 TET_LIB = os.path.join(PKG, "libmw_tet.so")
 TET_SRC = os.path.join(CSRC, "mw_tet.hip")
@@ -90,6 +92,11 @@ FLEX_DEPS = [FLEX_SRC, LIB_HOST, LIB_CELLS, LIB_FORCES, os.path.join(CSRC, "mw_c
 PIN_LIB = os.path.join(PKG, "libmw_pin.so")
 PIN_SRC = os.path.join(CSRC, "mw_pin.hip")
 PIN_DEPS = [PIN_SRC, LIB_HOST, LIB_CELLS, LIB_FORCES, os.path.join(CSRC, "mw_common.hip.h"), os.path.join(os.path.dirname(PKG), "include", "mw_pin.h")]
+
+NUC_LIB = os.path.join(PKG, "libmw_nuc.so")
+NUC_SRC = os.path.join(CSRC, "mw_nuc.hip")
+NUC_DEPS = [NUC_SRC, LIB_HOST, LIB_CELLS, LIB_FORCES, LIB_HARMONICS, os.path.join(CSRC, "mw_common.hip.h"),
+            os.path.join(os.path.dirname(PKG), "include", "mw_nuc.h"), os.path.join(os.path.dirname(PKG), "include", "mw_flex.h")]
 
 
 def hipcc_path():
@@ -203,7 +210,13 @@ def build_pin(force=False, verbose=False):
     return _compile(PIN_LIB, [PIN_SRC], PIN_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
 
 
+def build_nuc(force=False, verbose=False):
+    """libmw_nuc.so: nucleus-size molecular dynamics with on-device stopping rules and its C ABI, a translation unit of its own
+    like libmw_pin.so: the step of libmw_flex.so restated, with the l = 6 bond order and the cluster pass beside it."""
+    return _compile(NUC_LIB, [NUC_SRC], NUC_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
+
+
 if __name__ == "__main__":
     force = "--force" in sys.argv
-    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf, build_rings, build_md, build_npt, build_tcf, build_hess, build_ti, build_flex, build_pin, build_quench):
+    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf, build_rings, build_md, build_npt, build_tcf, build_hess, build_ti, build_flex, build_pin, build_nuc, build_quench):
         print(builder(force=force, verbose=True))

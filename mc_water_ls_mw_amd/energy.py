@@ -632,6 +632,19 @@ class EnergyModule:
         self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
         return pinning.interface_pinning(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, nvec, kappa, anchor, nsteps, dt, **kwargs)
 
+    # -- nucleus-size MD with on-device stopping rules (libmw_nuc.so, include/mw_nuc.h; no counterpart in the reference) --
+    def nucleus_md(self, first_ils=1, count=None, nsteps=0, dt=1.0, **kwargs):
+        """The eleven results of nucleation.nucleus_md -- the seven of :meth:`molecular_dynamics_flex` with a trace of 18
+        columns and the status codes 3 and 4 of the stopping rule, then nn, label and op -- from the positions the DEVICE holds
+        and this module's hmatrix; the keywords are those of nucleation.nucleus_md.  The engine's own positions and cells stay
+        as they are."""
+        from . import nucleation
+        count = self.num_lattices - first_ils + 1 if count is None else count
+        self._ils(first_ils), self._ils(first_ils + count - 1)
+        pos = np.zeros((count, self.nwater, 3))
+        self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
+        return nucleation.nucleus_md(self.hmatrix[first_ils - 1:first_ils - 1 + count], pos, nsteps, dt, **kwargs)
+
     # -- Einstein-crystal thermodynamic integration (libmw_ti.so, include/mw_ti.h; no counterpart in the reference) ------
     def einstein_md(self, ils, lambdas, springs, nsteps, dt, sites=None, **kwargs):
         """(pos_out, vel_out, forces [nl, nwater, 3], trace [nl, nsteps // sample_every + 1, 5], blocks [nl, nblocks, 5], status

@@ -545,6 +545,24 @@ class WalkerFarm:
         return (pos_out.reshape(*shape, self.em.nwater, 3), vel_out.reshape(*shape, self.em.nwater, 3), cells_out.reshape(*shape, 3, 3),
                 trace.reshape(*shape, -1, 15), status.reshape(*shape, 2))
 
+    def nucleus_md(self, nsteps, dt, first_global_walker=0, **kwargs):
+        """(pos_out, vel_out [nwalkers, nlat, nwater, 3], cells_out [nwalkers, nlat, 3, 3], trace [nwalkers, nlat, nsteps //
+        sample_every + 1, 18], status [nwalkers, nlat, 2], op [nwalkers, nlat, 4]): :meth:`molecular_dynamics_flex` with the size of
+        the largest solid-like cluster of every box watched and the stopping rule of include/mw_nuc.h (``lam_lo``, ``lam_hi``: one
+        value for every box, or one per box in the order walker, lattice), with the keywords of nucleation.nucleus_md
+        (``pressure`` defaults to the farm's own) and the same noise streams.  For farms of more than 64 molecules; a smaller one
+        gets the library's own message.  The walkers' own configurations and cells are left alone."""
+        if "streams" in kwargs:
+            raise ValueError("the farm names the noise streams itself: (first_global_walker + walker) * nlat + lattice")
+        self.sync_cells()
+        nb = self.em.num_lattices
+        streams = np.uint64(int(first_global_walker) * self.nlat) + np.arange(nb, dtype=np.uint64)
+        kwargs.setdefault("pressure", self.pressure)
+        pos_out, vel_out, _, cells_out, _, trace, status, _, _, op = self.em.nucleus_md(1, nb, nsteps, dt, streams=streams, **kwargs)
+        shape = (self.nwalkers, self.nlat)
+        return (pos_out.reshape(*shape, self.em.nwater, 3), vel_out.reshape(*shape, self.em.nwater, 3), cells_out.reshape(*shape, 3, 3),
+                trace.reshape(*shape, *trace.shape[1:]), status.reshape(*shape, 2), op.reshape(*shape, 4))
+
     def interface_pinning(self, nvec, kappa, anchor, nsteps, dt, first_global_walker=0, **kwargs):
         """(pos_out, vel_out [nwalkers, nlat, nwater, 3], cells_out [nwalkers, nlat, 3, 3], trace [nwalkers, nlat, nsteps //
         sample_every + 1, 17], blocks [nwalkers, nlat, nblocks, 4], status [nwalkers, nlat, 2]): :meth:`molecular_dynamics_flex`
