@@ -58,8 +58,8 @@
  * partial sums and the centres); a box that does not fit alone is an error.  The host-pointer entry stages the whole
  * trajectory on the device, outside that budget.
  *
- * Out of scope: collective F(k, t) and the distinct van Hove function, per-molecule mobilities, multiple-tau schemes,
- * stress correlations, a Fortran binding.
+ * Out of scope: collective F(k, t) and the distinct van Hove function (libmw_coll.so has them: include/mw_coll.h),
+ * per-molecule mobilities, multiple-tau schemes, stress correlations, a Fortran binding.
  *
  * Every function returns 0, or nonzero with the reason in mw_tcf_last_error().  Arguments are checked before the library's
  * state, so a call with bad arguments says so with or without a device; frame, box and list indices in messages count from 0.

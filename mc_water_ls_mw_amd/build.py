@@ -8,7 +8,9 @@ functions of trajectories, include/mw_tcf.h), libmw_hess.so (the Hessian of the 
 include/mw_hess.h), libmw_ti.so (Einstein-crystal thermodynamic integration, include/mw_ti.h), libmw_flex.so (molecular
 dynamics at constant pressure with a per-axis cell and the pressure tensor, include/mw_flex.h), libmw_pin.so (interface
 pinning: that step with a bias on a collective density mode, include/mw_pin.h) and libmw_nuc.so (that step with the size of the
-largest solid-like cluster watched and stopping rules on the device, include/mw_nuc.h) in-tree with hipcc for gfx950.
+largest solid-like cluster watched and stopping rules on the device, include/mw_nuc.h) and libmw_coll.so (collective time
+correlations of trajectories: F(k, t), the distinct van Hove function and the overlap sums, include/mw_coll.h) in-tree with
+hipcc for gfx950.
 
     python -m mc_water_ls_mw_amd.build [--force]
 
@@ -97,6 +99,10 @@ NUC_LIB = os.path.join(PKG, "libmw_nuc.so")
 NUC_SRC = os.path.join(CSRC, "mw_nuc.hip")
 NUC_DEPS = [NUC_SRC, LIB_HOST, LIB_CELLS, LIB_FORCES, LIB_HARMONICS, os.path.join(CSRC, "mw_common.hip.h"),
             os.path.join(os.path.dirname(PKG), "include", "mw_nuc.h"), os.path.join(os.path.dirname(PKG), "include", "mw_flex.h")]
+
+COLL_LIB = os.path.join(PKG, "libmw_coll.so")
+COLL_SRC = os.path.join(CSRC, "mw_coll.hip")
+COLL_DEPS = [COLL_SRC, LIB_HOST, os.path.join(os.path.dirname(PKG), "include", "mw_coll.h")]   # no cell grid and no shared device header
 
 
 def hipcc_path():
@@ -216,7 +222,13 @@ def build_nuc(force=False, verbose=False):
     return _compile(NUC_LIB, [NUC_SRC], NUC_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
 
 
+def build_coll(force=False, verbose=False):
+    """libmw_coll.so: the collective time-correlation kernels and their C ABI, a translation unit of its own over the libraries'
+    host layer alone, like libmw_tcf.so; the density modes restate libmw_sk.so's arithmetic, the pair pass mw_rdf's."""
+    return _compile(COLL_LIB, [COLL_SRC], COLL_DEPS, HIPCC_FLAGS, force=force, verbose=verbose)
+
+
 if __name__ == "__main__":
     force = "--force" in sys.argv
-    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf, build_rings, build_md, build_npt, build_tcf, build_hess, build_ti, build_flex, build_pin, build_nuc, build_quench):
+    for builder in (build, build_comms, build_sk, build_boo, build_tet, build_adf, build_rings, build_md, build_npt, build_tcf, build_hess, build_ti, build_flex, build_pin, build_nuc, build_coll, build_quench):
         print(builder(force=force, verbose=True))

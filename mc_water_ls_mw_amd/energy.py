@@ -693,6 +693,34 @@ class EnergyModule:
         out = timecorr.time_correlations_torch(frames, vel_frames if with_vacf else None, nlags, origin_every, q, edges, hist_lags, remove_com)
         return tuple(None if t is None else t.cpu().numpy() for t in out), status.cpu().numpy()
 
+    # -- collective time correlations (libmw_md.so records, libmw_coll.so correlates; include/mw_coll.h) -----------------
+    def collective_correlations(self, first_ils=1, count=None, nframes=2, steps_per_frame=1, dt=1.0, nlags=None, origin_every=1, nvec=None,
+                                r_max=0.0, nbins=0, hist_lags=(), overlap_a=0.0, outputs=("fkt", "gd", "qsum", "q2sum"), **md_keywords):
+        """((rho, fkt, gd, qsum, q2sum), status [count, 2]) of ``count`` boxes: a recorded molecular-dynamics run of ``nframes``
+        frames, ``steps_per_frame`` steps of ``dt`` apart (dynamics.trajectory with the keywords kT, gamma, vel, mass, seed,
+        streams, step0), from the positions the DEVICE holds and this module's hmatrix, and its collective time correlations
+        (collective.collective_correlations_torch: host arrays; rho, the modes of every frame, only if ``outputs`` names it).
+        The positions take one host hop, as :meth:`time_correlations` takes them; the engine's own positions stay as they are."""
+        import torch
+        from . import collective, dynamics
+        count = self.num_lattices - first_ils + 1 if count is None else count
+        self._ils(first_ils), self._ils(first_ils + count - 1)
+        pos = np.zeros((count, self.nwater, 3))
+        self._chk(self.L.mw_download_positions_range(first_ils, count, _d(pos)))
+        dev = torch.device("cuda", dynamics._dev.device or 0)
+        up = lambda a, dtype=torch.float64: torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(dev).contiguous()   # noqa: E731
+        kw = dict(md_keywords)
+        if kw.get("vel") is not None:
+            kw["vel_t"] = up(np.asarray(kw["vel"], dtype=np.float64).reshape(count, self.nwater, 3))
+        kw.pop("vel", None)
+        if kw.get("streams") is not None:
+            kw["streams_t"] = up(np.ascontiguousarray(kw["streams"], dtype=np.uint64).view(np.int64), torch.int64)
+        kw.pop("streams", None)
+        cells = np.ascontiguousarray(self.hmatrix[first_ils - 1:first_ils - 1 + count], dtype=np.float64)
+        frames, _, _, status = dynamics.trajectory(up(cells), up(pos), nframes, steps_per_frame, dt, **kw)
+        out = collective.collective_correlations_torch(cells, frames, nlags, origin_every, nvec, r_max, nbins, hist_lags, overlap_a, outputs)
+        return tuple(None if t is None else t.cpu().numpy() for t in out), status.cpu().numpy()
+
     def model_energy_counts(self, ils):
         p, t = ctypes.c_longlong(0), ctypes.c_longlong(0)
         self._chk(self.L.mw_model_energy_counts(ils, ctypes.byref(p), ctypes.byref(t)))

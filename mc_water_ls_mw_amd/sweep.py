@@ -601,6 +601,27 @@ class WalkerFarm:
         return (mean(msd), mean(mqd), mean(vacf), mean(fs), None if hist is None else hist.reshape(*shape, *hist.shape[1:]).sum(axis=0),
                 status.reshape(*shape, 2))
 
+    def collective_correlations(self, nframes, steps_per_frame, dt, first_global_walker=0, **kwargs):
+        """(fkt [nlat, nlags, M], gd [nlat, nh, nbins], qsum, q2sum [nlat, nlags], status [nwalkers, nlat, 2]): the collective time
+        correlations (include/mw_coll.h) of a recorded molecular-dynamics run of ``nframes`` frames, ``steps_per_frame`` steps of
+        ``dt`` apart, from the configuration of every lattice of every walker -- with the keywords of
+        ``EnergyModule.collective_correlations`` (nlags, origin_every, nvec, r_max, nbins, hist_lags, overlap_a, kT, gamma, vel,
+        mass, seed, step0).  fkt is averaged over the walkers per lattice; gd, qsum and q2sum are summed: they are sums over
+        origins, and a walker is more origins (divide by nwalkers x the origins of a lag).  The noise streams are those of
+        :meth:`time_correlations`.  The walkers' own configurations are left alone.  A result nobody asked for is None."""
+        if "streams" in kwargs:
+            raise ValueError("the farm names the noise streams itself: (first_global_walker + walker) * nlat + lattice")
+        if "rho" in kwargs.get("outputs", ()):
+            raise ValueError("the farm does not return the modes of every frame; ask EnergyModule.collective_correlations for rho")
+        self.sync_cells()
+        nb = self.em.num_lattices
+        streams = np.uint64(int(first_global_walker) * self.nlat) + np.arange(nb, dtype=np.uint64)
+        (_, fkt, gd, qsum, q2sum), status = self.em.collective_correlations(1, nb, nframes, steps_per_frame, dt, streams=streams, **kwargs)
+        shape = (self.nwalkers, self.nlat)
+        split = lambda a: a.reshape(*shape, *a.shape[1:])                    # noqa: E731
+        total = lambda a: None if a is None else split(a).sum(axis=0)        # noqa: E731
+        return (None if fkt is None else split(fkt).mean(axis=0), total(gd), total(qsum), total(q2sum), status.reshape(*shape, 2))
+
     # -- chain synchronisation (mc_check_chain_synchronisation, mc_moves.F90:2217-2416) -------------------------
     def set_reference(self):
         """Remember the reference configuration (ref_hmatrix / ref_ljr of init.f90:90,106) from the host's current
