@@ -43,7 +43,7 @@ extern "C" {
 #define MW_DISPATCH_ICE      4
 #define MW_DISPATCH_RDF      5
 #define MW_DISPATCH_FAMILIES 6
-#define MW_DISPATCH_FIELDS   13
+#define MW_DISPATCH_FIELDS   14
 
 /* LDS-staged builds of mw_lds_plan */
 #define MW_LDS_ENERGY 0        /* k_model_energy, box staged in LDS (both MOMOUT builds)              */
@@ -408,7 +408,8 @@ int mw_sweep_lds_bytes(int nlat, int nwater, int nbins, int row_stride, int volu
  *            full-box pass (fresh), requests per work item (mchunk), work items, dynamic LDS, build (0 L2 gather, 1 LDS with
  *            self-images, 2 LDS without, 3 moment path), counts of this launch (0 there, 1 to be made on demand by mw_moves_counts,
  *            2 dropped), on-demand count passes launched since mw_init, requests the launch left to k_move_fallback (-1 until
- *            mw_moves_counts has read the number back)
+ *            mw_moves_counts has read the number back), the box (0-based) the upload's work list starts from, before its items are dealt
+ *            to the XCDs (the highest box with requests: boxes are served in descending order; the lowest with MW_MOVE_BOX_ORDER=asc)
  *   FORCES, ICE : ivcap, boxes, box staged in LDS, workgroups per box, dynamic LDS
  *   RDF    : ivcap, boxes, small-box geometry (one wavefront per box), workgroups per box, dynamic + static LDS, images per
  *            pair (1, 3, 9 or 27: the largest of the launch's boxes)

@@ -172,6 +172,9 @@ __device__ __forceinline__ void pair_terms(double r2, double& rinv, double& e1, 
 // -- what the i--j--k triplet sum of a molecule i next to j needs of j's other neighbours:
 //   sum_k g_k (u_i . u_k - c0)^2 = u_i^T S2 u_i - 2 c0 u_i . S1 + c0^2 S0.
 constexpr int kMomStride = 10;   // doubles per molecule (80 bytes: five 16-byte pieces -- the full-box pass writes them a wavefront at a time, in whole records: store_moments_wave)
+// (The records lie at this plain stride, where four in eight straddle a 128-byte line.  Packed three to 256 bytes -- offsets 0, 80,
+//  160 of a trio, one record in three straddling, 6.7 % more footprint -- the step measured SLOWER, 0.493 against 0.489 ms, and a
+//  128-byte stride was slower before that: profiles/r13_summary.md, tools/mom_gather.hip.  Not kept.)
 __device__ __forceinline__ void load_moments(const double* m, double (&M)[10])      // one molecule's record, as five 16-byte loads
 {
     const double2* m2 = reinterpret_cast<const double2*>(m);

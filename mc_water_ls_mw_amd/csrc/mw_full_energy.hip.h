@@ -107,10 +107,18 @@ __device__ __forceinline__ ListRsrc list_rsrc(const uint32_t* L, int N, int S)
 {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(L), 0, (int)((size_t)N * S * sizeof(uint32_t)), 0x00020000);
 }
+// AUX: the load's cache policy.  kListNt marks the stream non-temporal: the LDS-staged full-box pass reads every list entry exactly
+// once (220 MB per 512 boxes of 4096), through an L2 in which the partially written lines of the moment records wait for their other
+// halves (store_moments_wave) -- a stream that will not be read again is told not to displace them.
+constexpr int kListNt = 2;               // the `nt` bit of a buffer load's auxiliary word on gfx942 / gfx950
+#ifndef MW_LIST_NT
+#define MW_LIST_NT 1                     // (diagnostic build `nont` of tools/variants.py, -DMW_LIST_NT=0: the default policy, for A/B runs)
+#endif
+template <int AUX = 0>
 __device__ __forceinline__ uint32_t list_load(ListRsrc rs, uint32_t column_bytes, int slot, int N, int S)
 {
     const int s = slot < S ? slot : S - 1;                                   // (uniform; such a slot is never live)
-    return __builtin_amdgcn_raw_buffer_load_b32(rs, (int)column_bytes, s * N * (int)sizeof(uint32_t), 0);
+    return __builtin_amdgcn_raw_buffer_load_b32(rs, (int)column_bytes, s * N * (int)sizeof(uint32_t), AUX);
 }
 
 // `queue` points at this thread's column of an LDS array [QCAP + 1][BLOCK] (entry q at queue[q*BLOCK]:
@@ -128,7 +136,8 @@ __device__ __forceinline__ uint32_t list_load(ListRsrc rs, uint32_t column_bytes
 // `ent` (LEAN only): where a lane's list entries come from when not from the slot-major list in global memory -- the Monte Carlo driver's
 // small walkers keep their rows in LDS (`ent(s)` = entry s of this lane's molecule, 0 past its end; then rs / col are unused).
 struct ListFromGlobal { static constexpr bool kGlobal = true; __device__ uint32_t operator()(int) const { return 0u; } };
-template <int BLOCK, bool BATCH4, bool LEAN = false, int QCAP = kQCap, typename PosFn, typename IvFn, typename EntFn = ListFromGlobal>
+// LISTAUX: the cache policy of the list stream (list_load).
+template <int BLOCK, bool BATCH4, bool LEAN = false, int QCAP = kQCap, int LISTAUX = 0, typename PosFn, typename IvFn, typename EntFn = ListFromGlobal>
 __device__ __forceinline__ AtomSum atom_energy(ListRsrc rs, uint32_t col, uint32_t col_next, int mol, int n, int nmax, int c0min,
                                                int N, int S, uint32_t* __restrict__ queue, PosFn getpos, IvFn getiv,
                                                uint32_t (&cur)[8], double* __restrict__ mom_out = nullptr, EntFn ent = ListFromGlobal(),
@@ -136,7 +145,7 @@ __device__ __forceinline__ AtomSum atom_energy(ListRsrc rs, uint32_t col, uint32
 {
     constexpr bool kEnt = !std::is_same<EntFn, ListFromGlobal>::value;
     static_assert(!kEnt || LEAN, "list entries from a functor: the lean variant only");
-    auto entry = [&](int s) -> uint32_t { if constexpr (kEnt) return ent(s); else return list_load(rs, col, s, N, S); };
+    auto entry = [&](int s) -> uint32_t { if constexpr (kEnt) return ent(s); else return list_load<LISTAUX>(rs, col, s, N, S); };
     double xi, yi, zi;
     getpos(mol, xi, yi, zi);
 
@@ -152,7 +161,7 @@ __device__ __forceinline__ AtomSum atom_energy(ListRsrc rs, uint32_t col, uint32
             const uint32_t pc = last ? col_next : col;        // whose chunk comes next
             const int ps = last ? 0 : s0 + 8;
 #pragma unroll
-            for (int u = 0; u < 8; ++u) nxt[u] = list_load(rs, pc, ps + u, N, S);
+            for (int u = 0; u < 8; ++u) nxt[u] = list_load<LISTAUX>(rs, pc, ps + u, N, S);
         }
         if constexpr (BATCH4) {
         // four slots at a time: their gathers are issued together, then the four tests (a slot past the longest
@@ -356,6 +365,7 @@ void k_model_energy(const double* __restrict__ pos, const double* __restrict__ i
     const int w0 = __builtin_amdgcn_readfirstlane(wid);
     const int first_grp = w0 < G ? g0 + G - 1 - w0 : -1; // first tickets: one per wavefront (wave-uniform, in a scalar register)
     const int nstage = LDSPOS ? (3 * N + kStageTicket - 1) / kStageTicket : 0;
+    constexpr int kAux = (LDSPOS && MW_LIST_NT) ? kListNt : 0;           // (the L2-gather build of large boxes keeps the default policy: its position gathers live in L2)
 
     // first list reads of this wavefront's first group: nothing in them depends on the staged box, so they are in flight
     // while it is being staged (behind the barrier they would be one more exposed HBM round trip per workgroup)
@@ -369,7 +379,7 @@ void k_model_energy(const double* __restrict__ pos, const double* __restrict__ i
             if (t < a1) { col = (uint32_t)t * 4u; n_cur = nns[(size_t)b * N + t]; mol = order[(size_t)b * N + t]; }
             const ListRsrc r0 = list_rsrc(list + (size_t)b * S * N, N, S);
 #pragma unroll
-            for (int u = 0; u < 8; ++u) cur[u] = list_load(r0, col, u, N, S);
+            for (int u = 0; u < 8; ++u) cur[u] = list_load<kAux>(r0, col, u, N, S);
         }
     };
     int bi = blockIdx.y;                                 // the workgroup's current box, counted within the launch
@@ -419,12 +429,12 @@ void k_model_energy(const double* __restrict__ pos, const double* __restrict__ i
             AtomSum a;
             if constexpr (MOMOUT) {
                 double2 rec[5];
-                a = atom_energy<BLOCK, BATCH4>(rs, col, col_next, mol, act ? (n_cur & 0xff) : 0, cm & 0xff, cm >> 8, N, S,
-                                               queue, getpos, getiv, cur, nullptr, ListFromGlobal(), rec);
+                a = atom_energy<BLOCK, BATCH4, false, kQCap, kAux>(rs, col, col_next, mol, act ? (n_cur & 0xff) : 0, cm & 0xff, cm >> 8, N, S,
+                                                                    queue, getpos, getiv, cur, nullptr, ListFromGlobal(), rec);
                 store_moments_wave<BLOCK>(queue - lane, rec, act ? mol : -1, mom + (size_t)b * N * kMomStride, lane);
             } else {
-                a = atom_energy<BLOCK, BATCH4>(rs, col, col_next, mol, act ? (n_cur & 0xff) : 0, cm & 0xff, cm >> 8, N, S,
-                                               queue, getpos, getiv, cur);
+                a = atom_energy<BLOCK, BATCH4, false, kQCap, kAux>(rs, col, col_next, mol, act ? (n_cur & 0xff) : 0, cm & 0xff, cm >> 8, N, S,
+                                                                    queue, getpos, getiv, cur);
             }
             if (act) { np += (unsigned int)a.cnt; nt += (unsigned int)(a.cnt * (a.cnt - 1) / 2); }
             const double ge = dpp_wave_sum(act ? a.e : 0.0);             // fixed tree; total in lane 63

@@ -172,7 +172,7 @@ struct Ctx {
     int* d_mdecl = nullptr;        // [0], [1] counts (alternate launches), then {request, box} of the requests k_move_energy left to k_move_fallback
     int mdecl_par = 0;             // which count word the next launch uses (the fallback kernel zeroes the other)
     int4* d_mwork = nullptr;       // work items {box, begin, end, 0}
-    int mwork_cap = 0, mwork_n = 0;
+    int mwork_cap = 0, mwork_n = 0, mwork_first = -1;   // (mwork_first: the box the work list starts from, before the XCD dealing; for mw_last_dispatch)
     bool mlds = false;
     int mmode = 0;
     int m_boxlo = 0, m_boxhi = -1, m_minreq = 0;   // the uploaded requests: their boxes (0-based range) and the fewest requests any of them has

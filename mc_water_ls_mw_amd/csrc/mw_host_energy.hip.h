@@ -39,7 +39,9 @@ int launch_model_energy(int first, int count, bool with_mom = false, bool write_
     }
     const int wen = write_energy ? 1 : 0;
     // whole boxes staged in LDS, one workgroup per box: the workgroups are persistent, one per compute unit (its LDS holds
-    // one), each taking every g.cu-th box and reading its next box while the current one's tail drains
+    // one), each taking every g.cu-th box and reading its next box while the current one's tail drains.  The boxes go out in a fixed
+    // ASCENDING order (workgroup y: boxes y, y + g.cu, ...), and mw_moves_upload serves the step's trial moves in DESCENDING box
+    // order: the two are meant to be opposite, so that each launch starts on what the one before it touched last.
     dim3 grid(ge.nsplit, g.model_persist && ge.lds && ge.nsplit == 1 ? std::min(count, g.cu) : count);
     const int box0 = first - 1;
     auto launch = [&](auto kernel) {

@@ -85,8 +85,19 @@ int mw_moves_upload(int n, const int* ils, const int* imol, const double* trial_
     { const char* mk = std::getenv("MW_MOVE_MASKS"); g.move_masks = !(mk && mk[0] == '0'); }   // (and its bit 6)
     { const char* mg = std::getenv("MW_MOVE_GATE"); g.move_gate = !(mg && mg[0] == '0'); }     // (and its bit 7)
     { const char* mp = std::getenv("MW_MOVE_PAIRS32"); g.move_pairs32 = !(mp && mp[0] == '0'); }   // (and its bit 8)
+    // NEWEST BOXES FIRST: the work list holds the boxes in DESCENDING order.  The step's full-box pass, persistent, hands its boxes
+    // out in ascending order (launch_model_energy), so what it touched last -- the highest boxes' positions and the moment records it
+    // wrote for them -- is what the memory-side cache still holds when the move kernel starts: served first, those first-touch reads
+    // are hits where the ascending order found box 0 evicted by the ~0.5 GB of traffic since.  The next step's full-box pass in turn
+    // starts on the low boxes the move kernel served last.  No result depends on the order (a request's bits are its own).
+    // MW_MOVE_BOX_ORDER=asc restores the ascending order for A/B runs.
+    bool desc = true;
+    if (const char* bo = std::getenv("MW_MOVE_BOX_ORDER")) desc = !(bo[0] == 'a' || bo[0] == 'A');
     std::vector<int4> work;
-    for (int b = 0; b < g.nbox; ++b) {
+    std::vector<int> rank_of((size_t)g.nbox, 0);                 // rank among the boxes that have requests, counted from box 0 in EITHER order
+    { int r = 0; for (int b = 0; b < g.nbox; ++b) if (start[(size_t)b + 1] > start[b]) rank_of[(size_t)b] = r++; }
+    for (int bb = 0; bb < g.nbox; ++bb) {
+        const int b = desc ? g.nbox - 1 - bb : bb;
         const int s0 = start[b], cntb = start[(size_t)b + 1] - s0;
         if (cntb == 0) continue;
         const int nitems = (cntb + chunk - 1) / chunk;           // equal shares: no short item at the end of a box
@@ -95,18 +106,17 @@ int mw_moves_upload(int n, const int* ils, const int* imol, const double* trial_
             work.push_back(w);
         }
     }
+    const int first_box = work.empty() ? -1 : work[0].x;         // (before the XCD dealing, which starts every XCD's sequence at once)
     // XCD-aware order.  Workgroups are dealt to the 8 XCDs round-robin (workgroup w runs on XCD w % 8) and every XCD
     // has its own L2, so the work items of one box -- which all stage the same positions and walk the same list
     // rows -- are placed on ONE XCD, one after the other: slot k*8 + x holds the k-th item of the boxes with
-    // (box index) % 8 == x.  (When the eight sequences differ in length the tail is dealt out as it comes.)
+    // (box index) % 8 == x.  (When the eight sequences differ in length the tail is dealt out as it comes.)  A box's XCD is its
+    // ascending rank % 8 whichever way the list runs -- the XCD whose persistent full-box workgroup wrote its moments when all
+    // boxes have requests -- and each XCD's sequence follows the list's order: descending by default.
     if (getenv("MW_NO_XCD_ORDER") == nullptr && work.size() >= 16) {
         constexpr int kXcd = 8;
         std::vector<std::vector<int4>> seq(kXcd);
-        int boxrank = -1, lastbox = -1;
-        for (const int4& w : work) {
-            if (w.x != lastbox) { ++boxrank; lastbox = w.x; }      // rank among the boxes that have requests
-            seq[(size_t)(boxrank % kXcd)].push_back(w);
-        }
+        for (const int4& w : work) seq[(size_t)(rank_of[(size_t)w.x] % kXcd)].push_back(w);
         std::vector<int4> ordered;
         ordered.reserve(work.size());
         std::vector<size_t> at(kXcd, 0);
@@ -123,6 +133,7 @@ int mw_moves_upload(int n, const int* ils, const int* imol, const double* trial_
     if (trial_xyz) HIPCHK(hipMemcpyAsync(g.d_mtrial, tr.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
     g.mwork_n = (int)work.size();
+    g.mwork_first = first_box;
     g.mn = n;
     return 0;
 }
@@ -162,7 +173,7 @@ static int launch_moves(int mode)
         int* d = g.disp[MW_DISPATCH_MOVES];
         d[0] = g.ivcap; d[1] = g.mn; d[2] = g.mlds; d[3] = g.m_noself; d[4] = use_mom; d[5] = use_mom && fresh; d[6] = g.mchunk;
         d[7] = g.mwork_n; d[8] = (int)shmem; d[9] = use_mom ? 3 : (g.mlds ? (g.m_noself ? 2 : 1) : 0);
-        d[10] = g.mcnt_state; d[11] = g.mcnt_passes; d[12] = -1;
+        d[10] = g.mcnt_state; d[11] = g.mcnt_passes; d[12] = -1; d[13] = g.mwork_first;
     }
     // the requests the fused routine declined (a few hundred per million on thermal ice): batched routine, two wavefronts each (one per position)
     hipLaunchKernelGGL(mw::k_move_fallback, dim3(std::min(1024, (g.mn + 3) / 4)), dim3(256), 0, g.stream, g.d_pos, g.d_ivect, g.d_listm, g.d_nn,

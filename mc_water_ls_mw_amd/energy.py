@@ -66,7 +66,7 @@ ABI_SYMBOLS = (
 DISPATCH_FIELDS = {
     "build": ("ivcap", "boxes", "grid_boxes", "brute_boxes", "fused_sort", "legacy_search", "order_seg", "nseg", "lds_bytes"),
     "energy": ("ivcap", "boxes", "lds", "nsplit", "chunk", "grid_y", "moments", "lds_bytes", "block"),
-    "moves": ("ivcap", "requests", "mlds", "noself", "use_mom", "fresh", "mchunk", "items", "lds_bytes", "build", "counts", "count_passes", "declined"),
+    "moves": ("ivcap", "requests", "mlds", "noself", "use_mom", "fresh", "mchunk", "items", "lds_bytes", "build", "counts", "count_passes", "declined", "first_box"),
     "forces": ("ivcap", "boxes", "lds", "nsplit", "lds_bytes"),
     "ice": ("ivcap", "boxes", "lds", "nsplit", "lds_bytes"),
     "rdf": ("ivcap", "boxes", "small", "workgroups_per_box", "lds_bytes", "images"),

@@ -20,6 +20,8 @@ KNOWN = {"stamps": ["-DMW_SWEEP_STAMPS"], "spill": ["-DMW_SWEEP_WAVES_CAP=5"],
          "dnosw": ["-DMW_ABL_D_NOSW"],
          "dnoall": ["-DMW_ABL_D_NOBIN", "-DMW_ABL_D_NOSWEXP", "-DMW_ABL_D_NOEXP", "-DMW_ABL_D_NOWL", "-DMW_ABL_D_NOSW"],
          "frame": ["-DMW_ABL_NODECIDE", "-DMW_ABL_NOEVAL"],
+         # the full-box pass's list stream at the default cache policy instead of non-temporal (mw_full_energy.hip.h: kListNt), for A/B runs
+         "nont": ["-DMW_LIST_NT=0"],
          # a volume move's split full-box energy checked against the one-wavefront routine inside the kernel (stamps 43..47)
          "splitcheck": ["-DMW_SWEEP_STAMPS", "-DMW_SPLIT_CHECK"]}
 
